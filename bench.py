@@ -18,7 +18,14 @@ observed world size, backend and every rank's own figures.  GGRS_BENCH_BACKEND=g
 ranks on fewer GPUs (ranks share devices).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-step F]
+    python bench.py --full ...         # + every-lane parity against the oracle and the CPU baselines
+    python bench.py --dump-outputs DIR # + the last step's outputs as DIR/<name>.npy
     python bench.py --config 3|4 ...   # speculative branch rollback
+
+A plain run of the default workload sets up, warms up, times the K steps and prints the line (its
+`parity` and `cpu_baseline` null); the parity leg and the CPU baselines, which take longer than the
+steps themselves, run with `--full`.  The inputs are a function of the arguments alone, so two builds
+run with the same arguments can be compared through `--dump-outputs`.
 
 Configs 3 and 4 (branch engine): a step is one round -- speculate (every (session, branch) lane
 replays the window from its session's confirmed trunk with the branch generator's remote inputs)
@@ -84,6 +91,99 @@ def pmc_valu(workload):
                 "wait_frac_of_wave_cycles": round(d["wait_any_frac"], 4), "profile": d.get("tag")}
     except Exception:
         return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: write what the timed path left after its last step as DIR/<name>.npy (float32;
+    float64 where float32 would not hold the values exactly), so two builds run with the same
+    arguments can be compared output for output.  Integer arrays here are bytes, u16 checksums and
+    small counts, all exact in float32."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype != np.float64:
+            a = a.astype(np.float64 if a.dtype.kind in "iu" and a.dtype.itemsize > 2 else np.float32)
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"--dump-outputs: {name} takes the dump past {DUMP_LIMIT_BYTES} bytes")
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(a))
+
+
+# the default workload's --full parity leg replays at most this many lane-frames on the CPU: every
+# lane of the default 4096 sessions x (20 + 5) steps x 512 frames, about 10 s on 16 threads
+PARITY_LANE_FRAMES = 4096 * 25 * 512
+
+
+class _LaneSubset:
+    """What oracle/every_lane.synctest reads of an Engine, restricted to the given lanes."""
+
+    def __init__(self, eng, lanes):
+        self.eng, self.lanes = eng, lanes
+
+    def states(self):
+        return self.eng.states()[self.lanes]
+
+    def save_checksums_frames(self, frames):
+        return [ck[self.lanes] for ck in self.eng.save_checksums_frames(frames)]
+
+    def trace(self, first_frame, n):
+        return self.eng.trace(first_frame, n)[:, self.lanes]
+
+
+def _i64(c):
+    """A u64 constant as the i64 with the same bits (torch has no u64 arithmetic)."""
+    c &= (1 << 64) - 1
+    return c - (1 << 64) if c >> 63 else c
+
+
+def held_inputs_chunks(torch, first_session, sessions, frames, players, device, chunk=None):
+    """synth.gen_inputs(first_session, sessions, frames, players, MODEL_HELD), bit for bit, computed
+    by torch on `device` in chunks of frames: yields (first frame, u8 tensor [n][sessions][players]).
+    The host generator walks the frames one by one (about 45 us each at 4096 sessions), which made
+    the bench's set-up grow with --steps; here draw k of session s is splitmix64's closed form
+    mix(base + s + (k + 1) G) in wrapping i64 arithmetic (logical shifts as arithmetic shift + mask),
+    and the held key is a forward fill along the frames (cummax over frame * 16 + value where a new
+    key is drawn), carried across chunks."""
+    from ggrs_amd import synth
+    G, M1, M2 = (_i64(int(c)) for c in (synth._G, synth._M1, synth._M2))
+    i64 = dict(dtype=torch.int64, device=device)
+    sess = torch.arange(first_session, first_session + sessions, **i64) + _i64(synth.SEED_BASE)
+    prev = torch.zeros((sessions, players), **i64)
+    chunk = chunk or max(16, (1 << 24) // (sessions * players))  # 16 M draws (128 MB of i64) at a time
+    for f0 in range(0, frames, chunk):
+        n = min(chunk, frames - f0)
+        k = torch.arange(f0, f0 + n, **i64)[:, None] * players + torch.arange(1, players + 1, **i64)[None, :]
+        z = sess[None, :, None] + (k * G)[:, None, :]
+        z = (z ^ ((z >> 30) & ((1 << 34) - 1))) * M1
+        z = (z ^ ((z >> 27) & ((1 << 37) - 1))) * M2
+        r = z ^ ((z >> 31) & ((1 << 33) - 1))
+        key = torch.arange(n, **i64)[:, None, None] * 16 + (r & 15)
+        key = key.masked_fill(((r >> 8) & 7) != 0, -1)  # the key is held: no new value at this frame
+        key = torch.cummax(key, dim=0).values
+        rows = torch.where(key >= 0, key & 15, prev[None].expand_as(key))
+        prev = rows[-1]
+        yield f0, rows.to(torch.uint8).contiguous()
+
+
+def dump_dir(args, rank):
+    return args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}")
+
+
+def box_state_arrays(states):
+    """[n][36 + 20 P] bincode state bytes (i32 frame, u64 num_players, then positions, velocities
+    and rotations each behind its u64 length) -> (frames [n] i32, fields [n][5 P] f32: the
+    players' (x, y)s, (vx, vy)s and rotations, bit for bit)."""
+    import numpy as np
+    b = np.ascontiguousarray(states)
+    P = (b.shape[1] - 36) // 20
+    assert b.shape[1] == 36 + 20 * P and P >= 1, b.shape
+    f32 = np.concatenate([b[:, 20:20 + 8 * P], b[:, 28 + 8 * P:28 + 16 * P], b[:, 36 + 16 * P:]], axis=1)
+    return np.ascontiguousarray(b[:, :4]).view("<i4")[:, 0], np.ascontiguousarray(f32).view("<f4")
 
 
 class FenceFreeEvents:
@@ -426,6 +526,12 @@ def run_branch(args):
     kernel_ms, launches = eng.timing_read()
     elapsed = t1 - t0
     n_desync = int(ex.desync_count.item()) if ex is not None else 0
+    if args.dump_outputs:
+        import numpy as np
+        ck, _ = eng.report()
+        frames_out, fields = box_state_arrays(np.stack([eng.trunk(s) for s in range(min(S, 1024))]))
+        dump_outputs(dump_dir(args, rank), {"report_checksums": ck, "survivors": eng.survivors(),
+                                            "trunk_state_fields": fields, "trunk_state_frames": frames_out})
     resim_round = L * W + S
     general = None
     if args.config == 3 and ex is None:
@@ -556,6 +662,12 @@ def run_particles(args):
     elapsed = t1 - t0
     elapsed, total, per_rank = rank_timings(dist, torch, elapsed, S * cd * args.steps)
     st, _, _ = eng.mismatches()
+    if args.dump_outputs:
+        import numpy as np
+        # a fixed, seeded sample of the 1 MB states: 8 sessions' state bytes (mixed-type fields)
+        pick = np.sort(np.random.default_rng(5).choice(S, size=min(S, 8), replace=False))
+        dump_outputs(dump_dir(args, rank), {"session_status": st, "sampled_sessions": pick,
+                                            "sampled_state_bytes": np.stack([eng.state(int(s)) for s in pick])})
     value = total / elapsed
     Sb = 4 + 100 * N
     bytes_launch = S * (Sb + cd * (Sb + 2) + 2 + 4 * (cd - 1) + (cd + 1) * P)
@@ -675,6 +787,10 @@ def run_p2p(args):
     rb1, rs1 = eng.stats()
     resim = int((rs1 - rs0).sum())
     rollbacks = int((rb1 - rb0).sum())
+    if args.dump_outputs:
+        frames_out, fields = box_state_arrays(eng.states())
+        dump_outputs(dump_dir(args, rank), {"final_state_fields": fields, "final_state_frames": frames_out,
+                                            "rollbacks": rb1, "resimulated_frames": rs1})
     value = total / elapsed
     F = 5 * P + 1
     skipped = errors = None
@@ -804,6 +920,12 @@ def run_codec(args):
     out, ln, dec, cnt, st = res
     ln_h = ln.cpu().numpy()
     pkt_bytes = int(ln_h.sum())
+    if args.dump_outputs:
+        # every packet's length, decoded count and status, and the first 65,536 packets' decoded
+        # inputs (the packet buffer itself holds unwritten bytes between packets)
+        dump_outputs(dump_dir(args, rank), {
+            "packet_lengths": ln_h, "decoded_counts": cnt.cpu().numpy(), "decode_status": st.cpu().numpy(),
+            "decoded_inputs_head": dec[:1 << 16].cpu().numpy()})
     ok = bool((st == 0).all().item()) and bool((cnt == d_cnt).all().item()) and bool((dec == d_pend).all().item())
     value = total / elapsed
     # algorithmic HBM bytes: encode reads ref + pending + count, writes packets + lengths; decode
@@ -1280,6 +1402,9 @@ def run_requests(args):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     n_calls = args.steps * calls
+    if args.dump_outputs:
+        frames_out, fields = box_state_arrays(np.concatenate([e.states() for e in engs]))
+        dump_outputs(dump_dir(args, rank), {"final_state_fields": fields, "final_state_frames": frames_out})
     if form == "p2p":
         # session-frames: every call of every lane; resimulated: the AdvanceFrames of the rollbacks
         m_of = np.arange(L) % fx["M"]
@@ -1426,6 +1551,15 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = min(16, cores available)")
     ap.add_argument("--cpu-frames", type=int, default=3000000,
                     help="SyncTest frames per CPU thread (default: ~10 s of host work)")
+    ap.add_argument("--full", action="store_true",
+                    help="the default workload (SyncTest config 2): after the timed steps also run the every-lane "
+                         "parity leg against the oracle and the CPU baselines (about half a minute of host "
+                         "work; past the default steps' lanes x frames the parity leg replays evenly spaced "
+                         "lanes); without it the line's parity and cpu_baseline are null.  The other workloads "
+                         "and configs always run theirs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed in its last step as "
+                         "DIR/<name>.npy (float32/float64; rank r > 0 writes DIR/rank<r>/)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--path", choices=["pipelined", "sequential", "chains", "batched"], default="pipelined",
                     help="SyncTest kernel (DESIGN.md section 3)")
@@ -1520,12 +1654,30 @@ def main():
     assert args.warmup * fps > cd, "warm-up must cover the first check_distance frames"
     trace_cap = min(256, total_frames)
 
-    inputs = synth.gen_inputs(rank * lanes, lanes, total_frames, P, synth.MODEL_HELD)
     eng = Engine(lanes, P, maxp, cd, delay, input_capacity=total_frames + cd + delay + 2,
                  device=local_rank, trace_capacity=trace_cap)
     eng.set_synctest_path({"pipelined": 0, "sequential": 1, "chains": 2, "batched": 3}[args.path])
-    eng.add_local_inputs(0, inputs)  # resident in HBM before anything is timed
-    eng.synchronize()
+    # the inputs of synth.gen_inputs(rank * lanes, lanes, total_frames, P, MODEL_HELD), generated on
+    # the device and queued from there: resident in HBM before anything is timed.  --full keeps a
+    # host copy of the lanes its parity leg replays on the CPU: every lane while the oracle's work
+    # (lanes x frames) stays within that of the default 25 steps, else evenly spaced lanes, the
+    # first and the last among them
+    import numpy as np
+    parity_lanes = None
+    if rank == 0 and args.full:
+        n_par = min(lanes, max(2, PARITY_LANE_FRAMES // total_frames))
+        parity_lanes = np.unique(np.linspace(0, lanes - 1, n_par).round().astype(np.int64))
+    dev = torch.device("cuda", local_rank)
+    sel = None if parity_lanes is None else torch.from_numpy(parity_lanes).to(dev)
+    kept = []
+    for f0, rows in held_inputs_chunks(torch, rank * lanes, lanes, total_frames, P, dev):
+        torch.cuda.synchronize(dev)  # the engine's stream reads what torch's stream wrote
+        eng.add_local_inputs_device(f0, rows.shape[0], rows.data_ptr())
+        eng.synchronize()            # ... before torch reuses the chunk's memory
+        if sel is not None:
+            kept.append(rows.index_select(1, sel).cpu().numpy())
+    inputs = np.concatenate(kept) if kept else None  # [total_frames][len(parity_lanes)][P]
+    del kept, sel
 
     def barrier():
         eng.synchronize()
@@ -1568,17 +1720,25 @@ def main():
                 "note": "issue/latency-bound step kernel (f32 step + f64 glibc sincosf, one wave per "
                         "SIMD); the 2 MB ring fits L2/MALL, so HBM traffic is below the algorithmic bytes"}
 
+    if args.dump_outputs:
+        frames_out, fields = box_state_arrays(eng.states())
+        dump_outputs(dump_dir(args, rank), {
+            "final_state_fields": fields, "final_state_frames": frames_out,
+            "checksum_trace": eng.trace(total_frames - trace_cap, trace_cap), "lane_status": status})
+
     parity = None
     cpu_baseline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             from oracle import oracle as O  # checker + CPU baseline only
             O.build()
             from oracle import every_lane
-            # EVERY lane against the oracle's SyncTestSession (oracle_synctest_batch on the job's
-            # CPU share): final state, ring checksums, the trace's last trace_cap frames
-            parity = every_lane.synctest(eng, inputs, P, maxp, cd, delay, trace_first=total_frames - trace_cap,
-                                         trace_n=trace_cap)
+            # EVERY lane (of parity_lanes: all of them at the default step counts) against the
+            # oracle's SyncTestSession (oracle_synctest_batch on the job's CPU share): final state,
+            # ring checksums, the trace's last trace_cap frames
+            parity = every_lane.synctest(_LaneSubset(eng, parity_lanes), inputs, P, maxp, cd, delay,
+                                         trace_first=total_frames - trace_cap, trace_n=trace_cap)
+            parity["lanes_of"] = lanes
             parity["every_lane_bit_exact"] = all(v == 0 for k, v in parity.items() if k.endswith("_mismatched"))
             if world == 1 and not args.no_cpu_baseline:
                 threads = cpu_threads(args)
