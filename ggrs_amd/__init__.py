@@ -13,5 +13,6 @@ from .handler import BatchedHandler, GameStateCell  # noqa: F401
 from .branch import BranchEngine  # noqa: F401
 from .particles import ParticleEngine  # noqa: F401
 from .p2p import P2PEngine  # noqa: F401
+from .spectator import SpectatorEngine  # noqa: F401
 
 __version__ = "0.1.0"

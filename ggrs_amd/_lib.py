@@ -18,6 +18,7 @@ GGRS_E_INVALID = -1
 GGRS_E_PRECONDITION = -2
 GGRS_E_HIP = -3
 GGRS_E_STATE = -4
+GGRS_E_TOO_FAR_BEHIND = -5
 NULL_FRAME = -1
 REQ_SAVE, REQ_LOAD, REQ_ADVANCE = 0, 1, 2
 STATUS_CONFIRMED, STATUS_PREDICTED, STATUS_DISCONNECTED = 0, 1, 2
@@ -57,6 +58,11 @@ EXPORTS = (
     "ggrs_p2p_set_desync_detection", "ggrs_p2p_local_checksums", "ggrs_p2p_compare_checksums",
     "ggrs_p2p_debug_desync", "ggrs_p2p_set_sparse_saving", "ggrs_p2p_set_unstaged",
     "ggrs_p2p_set_arrival_schedule", "ggrs_p2p_add_arrivals", "ggrs_p2p_read_sessions", "ggrs_p2p_read_reports", "ggrs_p2p_read_states", "ggrs_p2p_add_peer_reports",
+    "ggrs_spectator_engine_create", "ggrs_spectator_engine_destroy", "ggrs_spectator_engine_config",
+    "ggrs_spectator_add_inputs", "ggrs_spectator_add_arrivals", "ggrs_spectator_advance_frames",
+    "ggrs_spectator_calls", "ggrs_spectator_synchronize", "ggrs_spectator_read_sessions",
+    "ggrs_spectator_read_state", "ggrs_spectator_read_states", "ggrs_spectator_read_trace",
+    "ggrs_spectator_timing_reset", "ggrs_spectator_timing_stop", "ggrs_spectator_timing_read",
     "ggrs_codec_encode", "ggrs_codec_decode", "ggrs_codec_encode_chunked", "ggrs_codec_decode_chunked", "ggrs_codec_max_packet_bytes", "ggrs_codec_set_direct",
 )
 

@@ -5,7 +5,8 @@ against GGRS reads the same here; every object drives ALL lanes of one engine (o
 (session, branch)), so inputs carry a leading lane axis.
 
   SessionBuilder          src/sessions/builder.rs:30-78 (defaults :13-27), with_* :120-200,
-                          start_synctest_session :346-358
+                          start_synctest_session :346-358, with_max_frames_behind /
+                          with_catchup_speed :214-248, start_spectator_session :310-338
   SyncTestSession         src/sessions/sync_test_session.rs:11-218
   GgrsRequest variants    src/lib.rs:171-195 (SaveGameState, LoadGameState, AdvanceFrame)
   BoxGameHandler          the user's request handler, examples/ex_game/ex_game.rs:79-127
@@ -28,6 +29,9 @@ DEFAULT_PLAYERS = 2
 DEFAULT_INPUT_DELAY = 0
 DEFAULT_MAX_PREDICTION_FRAMES = 8
 DEFAULT_CHECK_DISTANCE = 2
+DEFAULT_MAX_FRAMES_BEHIND = 10
+DEFAULT_CATCHUP_SPEED = 1
+SPECTATOR_BUFFER_SIZE = 60  # p2p_spectator_session.rs:18
 
 
 class MismatchedChecksum(GgrsError):
@@ -380,6 +384,8 @@ class SessionBuilder:
         self.device = 0
         self.input_capacity = 0
         self.trace_capacity = 0
+        self.max_frames_behind = DEFAULT_MAX_FRAMES_BEHIND
+        self.catchup_speed = DEFAULT_CATCHUP_SPEED
 
     def with_num_players(self, n):
         self.num_players = n
@@ -412,6 +418,31 @@ class SessionBuilder:
     def with_trace_capacity(self, frames):
         self.trace_capacity = frames
         return self
+
+    def with_max_frames_behind(self, max_frames_behind):
+        """builder.rs:214-229 (checked here, as the reference's with_* returns the error)."""
+        if max_frames_behind < 1:
+            raise InvalidRequest(-1, "Max frames behind cannot be smaller than 1.")
+        if max_frames_behind >= SPECTATOR_BUFFER_SIZE:
+            raise InvalidRequest(-1, "Max frames behind cannot be larger or equal than the Spectator buffer size (60)")
+        self.max_frames_behind = max_frames_behind
+        return self
+
+    def with_catchup_speed(self, catchup_speed):
+        """builder.rs:233-248: checked against the max_frames_behind set so far."""
+        if catchup_speed < 1:
+            raise InvalidRequest(-1, "Catchup speed cannot be smaller than 1.")
+        if catchup_speed >= self.max_frames_behind:
+            raise InvalidRequest(-1, "Catchup speed cannot be larger or equal than the allowed maximum frames behind host")
+        self.catchup_speed = catchup_speed
+        return self
+
+    def start_spectator_session(self):
+        """builder.rs:310-338 for num_lanes spectators at once: a SpectatorEngine (the host's stream
+        and each session's network come in through add_inputs / add_arrivals)."""
+        from .spectator import SpectatorEngine
+        return SpectatorEngine(self.num_lanes, self.num_players, self.max_frames_behind, self.catchup_speed,
+                               self.input_capacity, self.trace_capacity, self.device)
 
     def start_synctest_session(self):
         """builder.rs:346-358: InvalidRequest("Check distance too big.") if check >= max_pred."""

@@ -1,0 +1,180 @@
+"""Batched SpectatorSession over the engine's C ABI (include/ggrs_amd.h, ggrs_spectator_*).
+
+One SpectatorEngine holds S spectators, each following one host's confirmed input stream over its
+own network.  Each call of advance_frames(n) runs n x SpectatorSession::advance_frame
+(src/sessions/p2p_spectator_session.rs:103-129) + the ex_game handler for every session: the
+host's frames up to recv_upto arrive (Event::Input, :218-231), a session more than
+max_frames_behind frames behind advances catchup_speed frames, one that has nothing to advance
+waits (PredictionThreshold, :175-177), one whose host ran 60 frames ahead is lost
+(SpectatorTooFarBehind, :180-182).  The device decides per session; kernel: csrc/spectator.hip.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from ._lib import InvalidRequest
+
+SPECTATOR_BUFFER_SIZE = 60  # p2p_spectator_session.rs:17
+DEFAULT_MAX_FRAMES_BEHIND = 10  # builder.rs:22
+DEFAULT_CATCHUP_SPEED = 1  # builder.rs:23
+TOO_FAR_BEHIND = _lib.GGRS_E_TOO_FAR_BEHIND
+
+
+class SpectatorConfig(ctypes.Structure):
+    _fields_ = [
+        ("num_sessions", ctypes.c_int32),
+        ("num_players", ctypes.c_int32),
+        ("max_frames_behind", ctypes.c_int32),
+        ("catchup_speed", ctypes.c_int32),
+        ("input_capacity", ctypes.c_int32),
+        ("trace_capacity", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+    ]
+
+
+_bound = False
+
+
+def _bind(L):
+    global _bound
+    if _bound:
+        return
+    vp = ctypes.c_void_p
+    P = ctypes.POINTER
+    i32 = ctypes.c_int32
+    L.ggrs_spectator_engine_create.argtypes = [P(SpectatorConfig), P(vp)]
+    L.ggrs_spectator_engine_destroy.argtypes = [vp]
+    L.ggrs_spectator_engine_config.argtypes = [vp, P(SpectatorConfig)]
+    L.ggrs_spectator_add_inputs.argtypes = [vp, i32, i32, vp]
+    L.ggrs_spectator_add_arrivals.argtypes = [vp, i32, i32, vp, vp]
+    L.ggrs_spectator_advance_frames.argtypes = [vp, i32]
+    L.ggrs_spectator_calls.argtypes = [vp, P(i32)]
+    L.ggrs_spectator_synchronize.argtypes = [vp]
+    L.ggrs_spectator_read_sessions.argtypes = [vp, vp, vp, vp, vp]
+    L.ggrs_spectator_read_state.argtypes = [vp, i32, vp]
+    L.ggrs_spectator_read_states.argtypes = [vp, vp]
+    L.ggrs_spectator_read_trace.argtypes = [vp, i32, i32, vp, vp]
+    L.ggrs_spectator_timing_reset.argtypes = [vp]
+    L.ggrs_spectator_timing_stop.argtypes = [vp]
+    L.ggrs_spectator_timing_read.argtypes = [vp, P(ctypes.c_float), P(i32)]
+    for name in _lib.EXPORTS:
+        if name.startswith("ggrs_spectator_"):
+            getattr(L, name).restype = ctypes.c_int
+    _bound = True
+
+
+def spectator_note(player, frame):
+    """GGRS_SPECTATOR_NOTE: the host's input message reports `player` disconnected with last frame
+    `frame` (protocol.rs:575-585).  0 = no note."""
+    return 1 | player << 1 | (frame + 1) << 3
+
+
+def _vp(a):
+    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
+
+
+class SpectatorEngine:
+    """S spectator sessions, each of its own host."""
+
+    def __init__(self, num_sessions, num_players=2, max_frames_behind=DEFAULT_MAX_FRAMES_BEHIND,
+                 catchup_speed=DEFAULT_CATCHUP_SPEED, input_capacity=0, trace_capacity=0, device=0):
+        self._L = _lib.lib()
+        _bind(self._L)
+        cfg = SpectatorConfig(num_sessions, num_players, max_frames_behind, catchup_speed, input_capacity,
+                              trace_capacity, device)
+        h = ctypes.c_void_p()
+        _lib.check(self._L.ggrs_spectator_engine_create(ctypes.byref(cfg), ctypes.byref(h)))
+        self._h = h
+        self.num_sessions, self.num_players = num_sessions, num_players
+        self.max_frames_behind, self.catchup_speed = max_frames_behind, catchup_speed
+        self.trace_capacity = trace_capacity
+        self.state_bytes = 36 + 20 * num_players
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ggrs_spectator_engine_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def config(self):
+        cfg = SpectatorConfig()
+        _lib.check(self._L.ggrs_spectator_engine_config(self._h, ctypes.byref(cfg)))
+        return cfg
+
+    def add_inputs(self, first_frame, inputs):
+        """inputs [n][S][P]: the host's confirmed inputs of frames first_frame .. first_frame + n - 1
+        (send_confirmed_inputs_to_spectators, p2p_session.rs:716-745), in order from frame 0; the
+        engine keeps the newest input_capacity rows."""
+        a = np.ascontiguousarray(inputs, np.uint8)
+        if a.ndim != 3 or a.shape[1:] != (self.num_sessions, self.num_players):
+            raise InvalidRequest(-1, f"inputs must be [n][{self.num_sessions}][{self.num_players}]")
+        _lib.check(self._L.ggrs_spectator_add_inputs(self._h, first_frame, a.shape[0], _vp(a)))
+
+    def add_arrivals(self, first_call, recv_upto, notes=None):
+        """recv_upto [n][S] int32: the newest host frame each session's poll delivered by calls
+        first_call .. first_call + n - 1 (not bounded by the call: the host has its own clock);
+        notes [n][S] int32 (spectator_note(player, frame) or 0) or None."""
+        a = np.ascontiguousarray(recv_upto, np.int32)
+        if a.ndim != 2 or a.shape[1] != self.num_sessions:
+            raise InvalidRequest(-1, f"recv_upto must be [n][{self.num_sessions}]")
+        nt = None
+        if notes is not None:
+            nt = np.ascontiguousarray(notes, np.int32)
+            if nt.shape != a.shape:
+                raise InvalidRequest(-1, "notes must have recv_upto's shape")
+        _lib.check(self._L.ggrs_spectator_add_arrivals(self._h, first_call, a.shape[0], _vp(a), _vp(nt)))
+
+    def advance_frames(self, n=1):
+        _lib.check(self._L.ggrs_spectator_advance_frames(self._h, n))
+
+    def calls(self):
+        v = ctypes.c_int32()
+        _lib.check(self._L.ggrs_spectator_calls(self._h, ctypes.byref(v)))
+        return v.value
+
+    def synchronize(self):
+        _lib.check(self._L.ggrs_spectator_synchronize(self._h))
+
+    def sessions(self):
+        """(current_frame, last_recv, waited, errors) [S] int32 each: waited = the calls that
+        returned PredictionThreshold; errors 0, TOO_FAR_BEHIND, or the code the session stopped with."""
+        out = [np.zeros(self.num_sessions, np.int32) for _ in range(4)]
+        _lib.check(self._L.ggrs_spectator_read_sessions(self._h, *(_vp(a) for a in out)))
+        return tuple(out)
+
+    def state(self, session):
+        out = np.zeros(self.state_bytes, np.uint8)
+        _lib.check(self._L.ggrs_spectator_read_state(self._h, session, _vp(out)))
+        return out
+
+    def states(self):
+        """state(session) for every session, one transfer: [num_sessions][state_bytes]."""
+        out = np.zeros((self.num_sessions, self.state_bytes), np.uint8)
+        _lib.check(self._L.ggrs_spectator_read_states(self._h, _vp(out)))
+        return out
+
+    def trace(self, first_call, n):
+        """(advanced [n][S] uint8, checksums [n][S] uint16) of calls first_call .. first_call + n - 1:
+        the AdvanceFrame requests each call returned and the state's fletcher16 after it."""
+        adv = np.zeros((n, self.num_sessions), np.uint8)
+        cks = np.zeros((n, self.num_sessions), np.uint16)
+        _lib.check(self._L.ggrs_spectator_read_trace(self._h, first_call, n, _vp(adv), _vp(cks)))
+        return adv, cks
+
+    def timing_reset(self):
+        _lib.check(self._L.ggrs_spectator_timing_reset(self._h))
+
+    def timing_stop(self):
+        """Record the span's end behind the last launch without waiting (timing_read reports it)."""
+        _lib.check(self._L.ggrs_spectator_timing_stop(self._h))
+
+    def timing_read(self):
+        ms, n = ctypes.c_float(), ctypes.c_int32()
+        _lib.check(self._L.ggrs_spectator_timing_read(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value

@@ -56,7 +56,9 @@ extern "C" {
  * ggrs_p2p_read_sessions)
  * 5: desync detection under arrival schedules (ggrs_p2p_read_reports)
  * 6: bulk reads for every-lane checks (ggrs_read_states, ggrs_p2p_read_states, ggrs_branch_read_cells);
- * lockstep mode under arrival schedules, peers' disconnect reports (ggrs_p2p_add_peer_reports) */
+ * lockstep mode under arrival schedules, peers' disconnect reports (ggrs_p2p_add_peer_reports);
+ * added without a new version (nothing existing changed): the spectator engine and
+ * GGRS_E_TOO_FAR_BEHIND */
 #define GGRS_ABI_VERSION 6
 
 #define GGRS_OK 0
@@ -64,6 +66,7 @@ extern "C" {
 #define GGRS_E_PRECONDITION (-2) /* a reference assert! would have panicked */
 #define GGRS_E_HIP (-3)          /* HIP runtime error (message from hipGetErrorString) */
 #define GGRS_E_STATE (-4)        /* call not valid in the engine's current mode */
+#define GGRS_E_TOO_FAR_BEHIND (-5) /* GgrsError::SpectatorTooFarBehind, per session (ggrs_spectator_read_sessions) */
 
 #define GGRS_NULL_FRAME (-1) /* src/lib.rs:47 */
 
@@ -596,6 +599,92 @@ int ggrs_p2p_read_sessions(ggrs_p2p_engine_t* eng, int32_t* frames, int32_t* ski
  * pointer may be NULL. */
 int ggrs_p2p_read_reports(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, int32_t* frames,
                           uint16_t* checksums, int32_t* last_confirmed, int32_t* local_last);
+
+/* ---------------------------------------------------------------------------------------------
+ * Spectators: num_sessions independent SpectatorSessions (src/sessions/p2p_spectator_session.rs),
+ * each following one host's confirmed input stream over its own network, each call =
+ * SpectatorSession::advance_frame (:103-129) + the ex_game handler.  Kernel: spectator.hip.
+ * Per session: current_frame and last_recv_frame start at GGRS_NULL_FRAME (:66-67), the input
+ * buffer holds SPECTATOR_BUFFER_SIZE = 60 frames (:17), host_connect_status[k] = {disconnected,
+ * last_frame} per player.  Call c: (1) the host's confirmed frames (last_recv, recv_upto[c]] arrive
+ * (Event::Input :218-231; a value at or below what already arrived delivers nothing; the host runs on
+ * its own clock, so recv_upto is not bounded by the call index); (2) the call's connect-status note
+ * is merged into the host endpoint's status (UdpProtocol::on_input, src/network/protocol.rs:575-585:
+ * disconnected is sticky, last_frame takes the maximum), which the session copies only with an
+ * Event::Input -- at the first call at or after the note's own that delivers a new frame (:228-231);
+ * (3) n = last_recv - current_frame > max_frames_behind ? catchup_speed : 1 (:109-113); (4) n times,
+ * f = current_frame + 1 (inputs_at_frame :168-197): last_recv < f -> PredictionThreshold, nothing
+ * advances (counted in `waited`); last_recv >= f + 60 -> SpectatorTooFarBehind, for good
+ * (GGRS_E_TOO_FAR_BEHIND in the session's error; it still receives); else AdvanceFrame with input
+ * row f, player k InputStatus::Disconnected (ex_game input 4) iff disconnected[k] && last_frame[k] <
+ * f, and current_frame += 1.
+ * catchup_speed == 1 goes with any max_frames_behind in 1..59, otherwise catchup_speed <
+ * max_frames_behind (builder.rs:214-248).  Under that rule both error exits can only hit the first
+ * of a call's n iterations (n > 1 means more than n frames are waiting, and last_recv < f + 60 at the
+ * first iteration holds at the later ones), so the reference's dropping of already built requests
+ * on `?` (:118) is never observable.
+ * Per-session stops (as ggrs_p2p_add_arrivals' sessions; the others run on): a session that needs an
+ * input row no longer among the input_capacity rows held when its launch started stops with
+ * GGRS_E_PRECONDITION; an arrival naming a frame not yet added when its launch started stops the
+ * session with GGRS_E_INVALID.  A stopped session changes no more; its calls trace 0 advances. */
+typedef struct ggrs_spectator_config {
+  int32_t num_sessions;      /* S >= 1 */
+  int32_t num_players;       /* 1..4 (ex_game.rs:70) */
+  int32_t max_frames_behind; /* 1..59 (with_max_frames_behind, builder.rs:214-229; default 10) */
+  int32_t catchup_speed;     /* 1, or 2..max_frames_behind-1 (with_catchup_speed, :233-248; default 1) */
+  int32_t input_capacity;    /* input rows and arrival rows held; 0 = 256; >= 64 */
+  int32_t trace_capacity;    /* calls of (advanced, checksum) kept (0: none) */
+  int32_t device;
+} ggrs_spectator_config_t;
+
+typedef struct ggrs_spectator_engine ggrs_spectator_engine_t;
+
+/* host_connect_status as the host's input messages carry it (protocol.rs:575-585): `player`
+ * disconnected with last frame `frame` (>= -1).  0 = no note. */
+#define GGRS_SPECTATOR_NOTE(player, frame) (1 | (player) << 1 | ((frame) + 1) << 3)
+
+/* SessionBuilder::start_spectator_session (builder.rs:310-338) with the checks of
+ * with_max_frames_behind / with_catchup_speed (:214-248), SpectatorSession::new
+ * (p2p_spectator_session.rs:43-71), State::new (ex_game.rs:246-269) */
+int ggrs_spectator_engine_create(const ggrs_spectator_config_t* cfg, ggrs_spectator_engine_t** out);
+int ggrs_spectator_engine_destroy(ggrs_spectator_engine_t* eng);
+int ggrs_spectator_engine_config(const ggrs_spectator_engine_t* eng, ggrs_spectator_config_t* out);
+/* The host's confirmed inputs of frames [first_frame, first_frame + n_frames), as
+ * send_confirmed_inputs_to_spectators sends them (p2p_session.rs:716-745):
+ * inputs [n_frames][num_sessions][num_players], added in order from frame 0.  The engine keeps the
+ * newest input_capacity rows. */
+int ggrs_spectator_add_inputs(ggrs_spectator_engine_t* eng, int32_t first_frame, int32_t n_frames,
+                              const uint8_t* inputs);
+/* recv_upto [n_calls][num_sessions] i32: the newest host frame each session's poll_remote_clients
+ * (p2p_spectator_session.rs:133-156) delivered by each call; notes [n_calls][num_sessions] i32
+ * (GGRS_SPECTATOR_NOTE or 0; NULL: none).  Calls in order from 0, at most input_capacity calls ahead
+ * of the next call. */
+int ggrs_spectator_add_arrivals(ggrs_spectator_engine_t* eng, int32_t first_call, int32_t n_calls,
+                                const int32_t* recv_upto, const int32_t* notes);
+/* n_calls calls of SpectatorSession::advance_frame (:103-129) + the handler for every session, one
+ * launch; GGRS_E_INVALID when a call's arrival row is missing */
+int ggrs_spectator_advance_frames(ggrs_spectator_engine_t* eng, int32_t n_calls);
+/* advance_frame calls made */
+int ggrs_spectator_calls(const ggrs_spectator_engine_t* eng, int32_t* out);
+int ggrs_spectator_synchronize(ggrs_spectator_engine_t* eng);
+/* per session [num_sessions] i32 each, any pointer may be NULL: SpectatorSession::current_frame
+ * (:159-161), last_recv_frame (:222), the calls that returned PredictionThreshold (:175-177), and
+ * the session's error: 0, GGRS_E_TOO_FAR_BEHIND (:180-182), GGRS_E_PRECONDITION or GGRS_E_INVALID */
+int ggrs_spectator_read_sessions(ggrs_spectator_engine_t* eng, int32_t* current_frame, int32_t* last_recv,
+                                 int32_t* waited, int32_t* errors);
+/* a session's game state as bincode bytes (36 + 20 * num_players); every session's, one transfer:
+ * out[num_sessions][36 + 20 * num_players] */
+int ggrs_spectator_read_state(ggrs_spectator_engine_t* eng, int32_t session, uint8_t* out);
+int ggrs_spectator_read_states(ggrs_spectator_engine_t* eng, uint8_t* out);
+/* calls first_call .. first_call + n - 1 (run, among the last trace_capacity): advanced [n][num_sessions]
+ * u8 = the AdvanceFrame requests the call returned (:120-122), checksums [n][num_sessions] u16 =
+ * fletcher16 of the state after the call (ex_game.rs:121-126), whether it advanced or not.  Either
+ * pointer may be NULL. */
+int ggrs_spectator_read_trace(ggrs_spectator_engine_t* eng, int32_t first_call, int32_t n, uint8_t* advanced,
+                              uint16_t* checksums);
+int ggrs_spectator_timing_reset(ggrs_spectator_engine_t* eng);
+int ggrs_spectator_timing_stop(ggrs_spectator_engine_t* eng); /* as ggrs_timing_stop */
+int ggrs_spectator_timing_read(ggrs_spectator_engine_t* eng, float* total_ms, int32_t* launches);
 
 /* ---- Input wire codec, batched (src/network/compression.rs:14-182; bitfield-rle 0.2.1 runs,
  * bincode 1.3 fixint framing of EncodedInputSequence).  Replaces compression::encode / decode as

@@ -27,6 +27,7 @@ const UNITS: &[(&str, &[&str])] = &[
     ("p2p_sched.hip", ILP),
     ("codec.hip", NONE),
     ("lane_encode.cpp", NONE),
+    ("spectator.hip", ILP),
 ];
 
 fn main() {

@@ -11,6 +11,7 @@ pub const GGRS_E_INVALID: i32 = -1;
 pub const GGRS_E_PRECONDITION: i32 = -2;
 pub const GGRS_E_HIP: i32 = -3;
 pub const GGRS_E_STATE: i32 = -4;
+pub const GGRS_E_TOO_FAR_BEHIND: i32 = -5;
 
 pub const GGRS_NULL_FRAME: i32 = -1;
 
@@ -128,6 +129,18 @@ pub struct ggrs_p2p_config_t {
 }
 
 #[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct ggrs_spectator_config_t {
+    pub num_sessions: i32,
+    pub num_players: i32,
+    pub max_frames_behind: i32,
+    pub catchup_speed: i32,
+    pub input_capacity: i32,
+    pub trace_capacity: i32,
+    pub device: i32,
+}
+
+#[repr(C)]
 pub struct ggrs_engine_t {
     _private: [u8; 0],
 }
@@ -145,6 +158,16 @@ pub struct ggrs_particle_engine_t {
 #[repr(C)]
 pub struct ggrs_p2p_engine_t {
     _private: [u8; 0],
+}
+
+#[repr(C)]
+pub struct ggrs_spectator_engine_t {
+    _private: [u8; 0],
+}
+
+/// GGRS_SPECTATOR_NOTE: the host reports `player` disconnected with last frame `frame` (0 = no note).
+pub const fn spectator_note(player: i32, frame: i32) -> i32 {
+    1 | player << 1 | (frame + 1) << 3
 }
 
 extern "C" {
@@ -300,6 +323,27 @@ extern "C" {
         last_confirmed: *mut i32,
         local_last: *mut i32,
     ) -> i32;
+
+    // ---- spectators (src/sessions/p2p_spectator_session.rs), batched
+    pub fn ggrs_spectator_engine_create(cfg: *const ggrs_spectator_config_t, out: *mut *mut ggrs_spectator_engine_t) -> i32;
+    pub fn ggrs_spectator_engine_destroy(eng: *mut ggrs_spectator_engine_t) -> i32;
+    pub fn ggrs_spectator_engine_config(eng: *const ggrs_spectator_engine_t, out: *mut ggrs_spectator_config_t) -> i32;
+    pub fn ggrs_spectator_add_inputs(eng: *mut ggrs_spectator_engine_t, first_frame: i32, n_frames: i32,
+                                     inputs: *const u8) -> i32;
+    pub fn ggrs_spectator_add_arrivals(eng: *mut ggrs_spectator_engine_t, first_call: i32, n_calls: i32,
+                                       recv_upto: *const i32, notes: *const i32) -> i32;
+    pub fn ggrs_spectator_advance_frames(eng: *mut ggrs_spectator_engine_t, n_calls: i32) -> i32;
+    pub fn ggrs_spectator_calls(eng: *const ggrs_spectator_engine_t, out: *mut i32) -> i32;
+    pub fn ggrs_spectator_synchronize(eng: *mut ggrs_spectator_engine_t) -> i32;
+    pub fn ggrs_spectator_read_sessions(eng: *mut ggrs_spectator_engine_t, current_frame: *mut i32,
+                                        last_recv: *mut i32, waited: *mut i32, errors: *mut i32) -> i32;
+    pub fn ggrs_spectator_read_state(eng: *mut ggrs_spectator_engine_t, session: i32, out: *mut u8) -> i32;
+    pub fn ggrs_spectator_read_states(eng: *mut ggrs_spectator_engine_t, out: *mut u8) -> i32;
+    pub fn ggrs_spectator_read_trace(eng: *mut ggrs_spectator_engine_t, first_call: i32, n: i32, advanced: *mut u8,
+                                     checksums: *mut u16) -> i32;
+    pub fn ggrs_spectator_timing_reset(eng: *mut ggrs_spectator_engine_t) -> i32;
+    pub fn ggrs_spectator_timing_stop(eng: *mut ggrs_spectator_engine_t) -> i32;
+    pub fn ggrs_spectator_timing_read(eng: *mut ggrs_spectator_engine_t, total_ms: *mut f32, launches: *mut i32) -> i32;
 
     // ---- input wire codec, batched (src/network/compression.rs:14-182); device pointers
     pub fn ggrs_codec_encode(ref_: *const u8, pending: *const u8, count: *const i32, n_packets: i64,
