@@ -603,6 +603,13 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v4_kernel(PipeParams
 //     and stores their display checksums; the launch's last chain also writes the current state.
 // 16 lanes per session at cd 8 / two players: four sessions per wave, 1024 waves for 4096
 // sessions, one per SIMD; the batch adds about one step's work per 8 steps.
+// kSplit (two players): 128 threads per block, the same sessions per block.  A lone wave per SIMD
+// is one dependent issue chain with nothing to hide its latencies behind, so the core blocks are
+// split by function over two waves: wave 0 (the producer) runs the whole flow above but in a core
+// step only advances, rotates and hands every lane's post-advance state over in LDS; wave 1 (the
+// consumer) takes part in the core blocks only and does their saves -- Fletcher sums, first-seen
+// compare, stores -- and their batch, one block behind the producer.  One LDS-only workgroup
+// barrier per 8-step block, two hand-off buffers.
 // v5 step kinds: std::false_type the general step (raw input, per-step domain test, stores only for
 // the launch's chains), std::true_type the core step, EdgeStep the core step's arithmetic for the
 // launch's first and last steps (some roles hold chains of other launches: their stores write the
@@ -613,8 +620,8 @@ struct EdgeStep : std::true_type {};
 template <class T> struct IsEdge : std::false_type {};
 template <> struct IsEdge<EdgeStep> : std::true_type {};
 
-template <int P>
-__global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams p) {
+template <int P, bool kSplit>
+__global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined_v5_kernel(PipeParams p) {
   constexpr int Pp = P <= 1 ? 1 : (P == 2 ? 2 : 4);
   constexpr int F = state_fields(P);
   constexpr int n_bytes = Fletcher<P>::n;
@@ -629,13 +636,27 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
   // prologue beside every other global read: one memory latency per launch), and their decoded
   // InputRec for kStage5 frames at a time (+1 slack row for the batch's look-ahead), decoded from
   // LDS every kStage5 steps; the non-core steps read the raw bytes
-  constexpr int kStage5 = 128;
+  // (the split kernel stages half as many rows at a time: with its hand-off buffers a block then
+  // holds 39 KB of LDS, and four blocks -- eight waves, two per SIMD -- still share a CU's 160 KB)
+  constexpr int kStage5 = kSplit ? 64 : 128;
   constexpr int kRaw = 528;
   __shared__ __attribute__((aligned(16))) uint8_t lds_raw[kRaw * ROW];
   __shared__ uint4 lds_rec[(kStage5 + 1) * ROW];
   __shared__ uint16_t lds_first[CD * SPW];
   __shared__ __attribute__((aligned(16))) uint8_t lds_stash[2 * kB * kSlot];  // slots, then the dump
-  const int wl = threadIdx.x;
+  // Split kernel: the producer wave's hand-off to the consumer wave, two buffers of one 8-step
+  // block each.  A step's slot holds every lane's post-advance state (fields 0..3 as one uint4 per
+  // lane, then field 4 as one word per lane); lds_hrec holds, per buffer and lane, the InputRec
+  // the lane's batch sub-step needs (lds_rec itself is restaged while the consumer still works).
+  constexpr int kHSlot = kWave * 20;
+  __shared__ __attribute__((aligned(16))) uint8_t lds_hand[kSplit ? 2 * kB * kHSlot : 16];
+  __shared__ uint4 lds_hrec[kSplit ? 2 * kWave : 1];
+  __shared__ int32_t lds_ctl[2];  // split kernel: the number of core blocks and their first step
+  const int wl = threadIdx.x & (kWave - 1);
+  // wave 0 produces, wave 1 consumes (one-wave kernel: the only wave does both).  Measured
+  // (DESIGN.md §5): with wave 0 the producer in every block each SIMD gets one wave of each role;
+  // swapping the roles in every other block of a CU pairs producers and loses the whole gain.
+  const bool consumer = kSplit && __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave)) != 0;
   const int R = p.R;
   const int g = wl / G, r = wl - g * G;
   const int j = r / Pp, pl = r - j * Pp;  // static role, player
@@ -654,8 +675,10 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
   constexpr int kCkRegs = 16;  // checkpoint words per thread in the fast form
   constexpr int kRawRegs = (kRaw + kWave - 1) / kWave;
   const int ck_words32 = (1 + R) * F * SPW, ck_words16 = R * SPW;  // 16-bit rows as word pairs
-  const bool fast = nsess == SPW && ((L * Pp) & 7) == 0 && (L & 1) == 0 && ck_words32 + ck_words16 <= kCkRegs * kWave;
-  const int32_t failed_f0 = *p.fail_f0;
+  const bool fast = !consumer && nsess == SPW && ((L * Pp) & 7) == 0 && (L & 1) == 0 && ck_words32 + ck_words16 <= kCkRegs * kWave;
+  // only the producer reads *fail_f0 (another block's atomicCAS can land between two reads): the
+  // consumer learns what follows from it through lds_ctl
+  const int32_t failed_f0 = consumer ? -1 : *p.fail_f0;
   const int32_t lstat = p.lane_status[s < L ? s : L - 1];
   uint32_t ckv[kCkRegs];
   uint2 rawv[kRawRegs];
@@ -685,7 +708,7 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
       }
     }
   }
-  if (wl < CD * nsess) {
+  if (!consumer && wl < CD * nsess) {
     const int gg = wl / nsess, ss = wl - gg * nsess;
     const int32_t sl = slot_g0 + gg >= R ? slot_g0 + gg - R : slot_g0 + gg;
     firstv = p.first_ck[(int64_t)sl * L + s0 + ss];
@@ -736,14 +759,33 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
   const int32_t jm = j % tcap;
 
   // the cell of frame g0 (every role's Load): read straight into the lane's registers
-  uint32_t w[5];
-  {
+  uint32_t w[5] = {0u, 0u, 0u, 0u, 0u};
+  if (!consumer) {
     const uint32_t* cell = p.ring + (int64_t)slot_g0 * F * L + sl;
 #pragma unroll
     for (int q = 0; q < 5; q++) w[q] = cell[kq[q] * L];
   }
-  if (failed_f0 >= 0 && failed_f0 != p.f0) return;
-  {
+  // Split kernel, the block's barriers.  The producer calls publish() exactly once on every path
+  // (the early returns below: no core block), the consumer waits for it once; after it both waves
+  // know the number of core blocks nb and execute nb + 1 more barriers each (one per block's
+  // hand-off, one after the consumer's last store), none if nb == 0 -- so no path leaves a wave
+  // waiting for one that has returned.  The barriers wait for LDS only (s_waitcnt lgkmcnt(0)): a
+  // __syncthreads would also drain the consumer's ring stores in flight, once per block.
+  auto block_barrier = [] {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes and reads are done
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  auto publish = [&](int32_t nb, int32_t t0) {
+    if (wl == 0) lds_ctl[0] = nb, lds_ctl[1] = t0;
+    block_barrier();
+  };
+  if (failed_f0 >= 0 && failed_f0 != p.f0) {
+    if constexpr (kSplit) publish(0, 0);
+    return;
+  }
+  if (!consumer) {
     uint8_t* piece = p.shadow + blk * p.block_bytes;
     if (fast) {
 #pragma unroll
@@ -756,8 +798,11 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
       checkpoint_sessions(m, piece, s0, nsess, wl, kWave);
     }
   }
-  if (failed_f0 >= 0) return;
-  if (wl < CD * nsess) {
+  if (failed_f0 >= 0) {
+    if constexpr (kSplit) publish(0, 0);
+    return;
+  }
+  if (!consumer && wl < CD * nsess) {
     const int gg = wl / nsess, ss = wl - gg * nsess;
     lds_first[gg * SPW + ss] = firstv;
   }
@@ -768,12 +813,13 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
       const int ff = wl + i * kWave;
       if (ff < nraw) reinterpret_cast<uint2*>(lds_raw)[ff] = rawv[i];
     }
-  } else {
+  } else if (!consumer) {
     stage_input_rows<ROW>(lds_raw, p.inputs, L, Pp, p.cap, g0, nraw, s0, nsess * Pp, ROW, wl);
   }
-  // the block is one wave: LDS written by one lane and read by another needs only the wave's own
-  // in-order LDS queue and a compiler fence (a __syncthreads would also wait for the checkpoint's
-  // stores; inside the step loop, for every ring store in flight)
+  // lds_raw, lds_rec, lds_first and lds_stash belong to one wave (the split kernel's producer): LDS
+  // written by one lane and read by another needs only the wave's own in-order LDS queue and a
+  // compiler fence (a __syncthreads would also wait for the checkpoint's stores; inside the step
+  // loop, for every ring store in flight)
   auto wave_lds_sync = [] {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -825,7 +871,42 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
   uint32_t sc_qs = 0u, sc_qc = 0u;   // and their quadrant signs
 
   auto rec_of = [](const uint4 v) { return InputRec{v.x, v.y, v.z, v.w}; };
-  // core steps take the staged InputRec, non-core steps the raw input byte
+  // Fletcher-16 of a cell: its frame word and this lane's fields, combined over the player lanes
+  auto cell_checksum = [&](const uint32_t(&v)[5], uint32_t frame) -> uint32_t {
+    uint32_t d1 = dot4_u8(frame, wf1, c1), d2 = dot4_u8(frame, wf2, c2);
+#pragma unroll
+    for (int q = 0; q < 5; q++) {
+      d1 = dot4_u8(v[q], one2, d1);
+      d2 = dot4_u8(v[q], wt[q], d2);
+    }
+    if constexpr (Pp >= 2) {
+      d1 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d1, 0xB1, 0xF, 0xF, true);
+      d2 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d2, 0xB1, 0xF, 0xF, true);
+    }
+    if constexpr (Pp >= 4) {
+      d1 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d1, 0x4E, 0xF, 0xF, true);
+      d2 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d2, 0x4E, 0xF, 0xF, true);
+    }
+    return fletcher_from_doubled(d1, d2);
+  };
+  // role cd-1's first-seen checksum to every lane of the session (two players: DPP row_newbcast
+  // of the row's lane 14)
+  auto first_seen = [&](uint32_t ck) -> uint32_t {
+    return Pp == 2 ? (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ck, 0x150 + (CD - 1) * Pp, 0xF, 0xF, true)
+                   : (uint32_t)__builtin_amdgcn_ds_bpermute(src_first, (int)ck);
+  };
+  // a step's save: the cell, its frame and its checksum(s) into ring slot sru
+  auto store_cell = [&](const uint32_t(&v)[5], uint32_t frame, uint32_t ck, uint32_t sru) {
+    const uint32_t so = sru * slot_bytes, cso = sru * ck_slot_bytes;
+#pragma unroll
+    for (int q = 0; q < 5; q++) __builtin_amdgcn_raw_buffer_store_b32(v[q], rs_ring, fo[q], so, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(frame, rs_ring, fo_frame, so, 0);
+    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)ck, rs_ring, co, cso, 0);
+    if constexpr (!kMergedCk) __builtin_amdgcn_raw_buffer_store_b16((uint16_t)ck, rs_ring, co_first, cso, 0);
+  };
+  // core steps take the staged InputRec, non-core steps the raw input byte.  slot_off: the step's
+  // stash slot; in the split kernel's core steps (the producer's half of the step: the advance, the
+  // rotation and the hand-off) the step's hand-off slot
   auto step = [&](auto core_tag, int32_t t, auto in, uint32_t slot_off) {
     constexpr bool kCore = decltype(core_tag)::value;
     constexpr bool kEdge = IsEdge<decltype(core_tag)>::value;
@@ -855,7 +936,7 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
       w[3] = __builtin_bit_cast(uint32_t, vy);
       w[4] = __builtin_bit_cast(uint32_t, rot);
     }
-    if (kCore && !kEdge) acc |= pend_ck ^ pend_first;
+    if (kCore && !kEdge && !kSplit) acc |= pend_ck ^ pend_first;
     const uint32_t frame1 = (uint32_t)(t - CD + 1);
     // rotation: role j takes role j-1's state, role 0 keeps its own.  At two players a session is
     // one 16-lane DPP row (role j = lanes 2j, 2j+1): one row_shr:2 move per field, the row's first
@@ -866,77 +947,49 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
 #pragma unroll
       for (int q = 0; q < 5; q++) nx[q] = (uint32_t)__builtin_amdgcn_ds_bpermute(src_rot, (int)w[q]);
     }
-    // role cd-1's post-advance state for the batch (every other lane writes the dump)
-    {
-      uint8_t* st = lds_stash + stash_w + slot_off;
-      *reinterpret_cast<uint4*>(st) = make_uint4(w[0], w[1], w[2], w[3]);
-      *reinterpret_cast<uint32_t*>(st + 16) = w[4];
-    }
-    if constexpr (Pp != 2) __builtin_amdgcn_sched_barrier(0);  // LDS latency behind the sums
-    uint32_t d1 = dot4_u8(frame1, wf1, c1), d2 = dot4_u8(frame1, wf2, c2);
-#pragma unroll
-    for (int q = 0; q < 5; q++) {
-      d1 = dot4_u8(w[q], one2, d1);
-      d2 = dot4_u8(w[q], wt[q], d2);
-    }
-    if constexpr (Pp >= 2) {
-      d1 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d1, 0xB1, 0xF, 0xF, true);
-      d2 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d2, 0xB1, 0xF, 0xF, true);
-    }
-    if constexpr (Pp >= 4) {
-      d1 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d1, 0x4E, 0xF, 0xF, true);
-      d2 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d2, 0x4E, 0xF, 0xF, true);
-    }
-    const uint32_t ck = fletcher_from_doubled(d1, d2);
-    // role cd-1's first-seen checksum to every lane of the session (two players: DPP
-    // row_newbcast of the row's lane 14)
-    uint32_t first = Pp == 2 ? (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ck, 0x150 + (CD - 1) * Pp, 0xF, 0xF, true)
-                             : (uint32_t)__builtin_amdgcn_ds_bpermute(src_first, (int)ck);
-    if ((!kCore || kEdge) && rel + 1 < CD) first = lds_first[(rel + 1) * SPW + g];
-    const uint32_t sru = (uint32_t)sr;
-    auto stores = [&]() {
-      const uint32_t so = sru * slot_bytes, cso = sru * ck_slot_bytes;
-#pragma unroll
-      for (int q = 0; q < 5; q++) __builtin_amdgcn_raw_buffer_store_b32(w[q], rs_ring, fo[q], so, 0);
-      __builtin_amdgcn_raw_buffer_store_b32(frame1, rs_ring, fo_frame, so, 0);
-      __builtin_amdgcn_raw_buffer_store_b16((uint16_t)ck, rs_ring, co, cso, 0);
-      if constexpr (!kMergedCk) __builtin_amdgcn_raw_buffer_store_b16((uint16_t)ck, rs_ring, co_first, cso, 0);
-    };
-    if (kCore) {
-      stores();
-      pend_lanes = kEdge ? cmp_lanes & __ballot(active) : cmp_lanes;
+    if constexpr (kSplit && kCore && !kEdge) {
+      // every lane's post-advance state to the consumer, which checksums, compares and stores it
+      // and runs the block's batch from the role cd-1 entries (the caller advances sr)
+      uint8_t* st = lds_hand + slot_off;
+      *reinterpret_cast<uint4*>(st + wl * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+      *reinterpret_cast<uint32_t*>(st + kWave * 16 + wl * 4) = w[4];
     } else {
-      if (active) stores();
-      pend_lanes = cmp_lanes & __ballot(active);
+      // role cd-1's post-advance state for the batch (every other lane writes the dump)
+      {
+        uint8_t* st = lds_stash + stash_w + slot_off;
+        *reinterpret_cast<uint4*>(st) = make_uint4(w[0], w[1], w[2], w[3]);
+        *reinterpret_cast<uint32_t*>(st + 16) = w[4];
+      }
+      if constexpr (Pp != 2) __builtin_amdgcn_sched_barrier(0);  // LDS latency behind the sums
+      const uint32_t ck = cell_checksum(w, frame1);
+      uint32_t first = first_seen(ck);
+      if ((!kCore || kEdge) && rel + 1 < CD) first = lds_first[(rel + 1) * SPW + g];
+      if (kCore) {
+        store_cell(w, frame1, ck, (uint32_t)sr);
+        pend_lanes = kEdge ? cmp_lanes & __ballot(active) : cmp_lanes;
+      } else {
+        if (active) store_cell(w, frame1, ck, (uint32_t)sr);
+        pend_lanes = cmp_lanes & __ballot(active);
+      }
+      pend_ck = ck;
+      pend_first = first;
+      sr = sr + 1 == R ? 0 : sr + 1;
     }
-    pend_ck = ck;
-    pend_first = first;
 #pragma unroll
     for (int q = 0; q < 5; q++)
       w[q] = Pp == 2 ? (uint32_t)__builtin_amdgcn_update_dpp((int)w[q], (int)w[q], 0x112, 0xF, 0xF, false) : nx[q];
-    sr = sr + 1 == R ? 0 : sr + 1;
   };
 
   // The batch over the stashes of steps tb .. tb + count - 1 (count <= 8; tb - f0 a multiple of
   // 8): role j < count advances step tb + j's stash -- chain cb = tb + j - (cd - 1), its frame cb,
   // with input cb, which step tb + j + 1 reads -- and stores the display checksum of frame cb + 1.
-  auto batch = [&](auto core_tag, int32_t tb, int count) {
+  // batch_run: the sub-step itself, from the stashed state v and the input `in` (core: the
+  // InputRec, else the raw byte); batch: the one-wave form, which reads both from this wave's LDS.
+  auto batch_run = [&](auto core_tag, int32_t tb, int count, uint32_t(&v)[5], auto in) {
     constexpr bool kCore = decltype(core_tag)::value;
     constexpr bool kEdge = IsEdge<decltype(core_tag)>::value;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const int32_t cb = tb + j - (CD - 1);
     const bool act = (kCore && !kEdge) ? (valid && j < kB) : (valid && j < count && cb >= p.f0 && cb < p.f0 + p.n);
-    uint32_t v[5];
-    {
-      const uint8_t* st = lds_stash + stash_r;
-      const uint4 a = *reinterpret_cast<const uint4*>(st);
-      v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
-      v[4] = *reinterpret_cast<const uint32_t*>(st + 16);
-    }
-    const uint32_t ri = (uint32_t)(tb + (j & (kB - 1)) + 1 - chunk0) * ROW + in_at;
-    const uint32_t rr = (uint32_t)(tb + (j & (kB - 1)) + 1 - raw0) * ROW + in_at;
     {
       float x = __builtin_bit_cast(float, v[0]), y = __builtin_bit_cast(float, v[1]);
       float vx = __builtin_bit_cast(float, v[2]), vy = __builtin_bit_cast(float, v[3]);
@@ -945,9 +998,9 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
         float bs, bc;
         uint32_t bqs, bqc;
         glibc_sincosf_domain_raw(rot, &bs, &bc, &bqs, &bqc);
-        advance_player_rec_q(x, y, vx, vy, rot, rec_of(lds_rec[ri]), bs, bc, bqs, bqc);
+        advance_player_rec_q(x, y, vx, vy, rot, rec_of(in), bs, bc, bqs, bqc);
       } else {
-        advance_player(x, y, vx, vy, rot, lds_raw[rr]);
+        advance_player(x, y, vx, vy, rot, (uint32_t)in);
       }
       v[0] = __builtin_bit_cast(uint32_t, x);
       v[1] = __builtin_bit_cast(uint32_t, y);
@@ -956,21 +1009,7 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
       v[4] = __builtin_bit_cast(uint32_t, rot);
     }
     const uint32_t framen = (uint32_t)(cb + 1);
-    uint32_t d1 = dot4_u8(framen, wf1, c1), d2 = dot4_u8(framen, wf2, c2);
-#pragma unroll
-    for (int q = 0; q < 5; q++) {
-      d1 = dot4_u8(v[q], one2, d1);
-      d2 = dot4_u8(v[q], wt[q], d2);
-    }
-    if constexpr (Pp >= 2) {
-      d1 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d1, 0xB1, 0xF, 0xF, true);
-      d2 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d2, 0xB1, 0xF, 0xF, true);
-    }
-    if constexpr (Pp >= 4) {
-      d1 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d1, 0x4E, 0xF, 0xF, true);
-      d2 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d2, 0x4E, 0xF, 0xF, true);
-    }
-    const uint32_t ck = fletcher_from_doubled(d1, d2);
+    const uint32_t ck = cell_checksum(v, framen);
     int32_t ti = sb + jm;
     ti = ti >= tcap ? ti - tcap : ti;
     const uint32_t tro = act ? co_trace + (uint32_t)ti * ck_slot_bytes : kOob;
@@ -986,6 +1025,24 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
     sb = sb + sb_step;
     sb = sb >= tcap ? sb - tcap : sb;
   };
+  auto batch = [&](auto core_tag, int32_t tb, int count) {
+    constexpr bool kCore = decltype(core_tag)::value;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    uint32_t v[5];
+    {
+      const uint8_t* st = lds_stash + stash_r;
+      const uint4 a = *reinterpret_cast<const uint4*>(st);
+      v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
+      v[4] = *reinterpret_cast<const uint32_t*>(st + 16);
+    }
+    if constexpr (kCore) {
+      batch_run(core_tag, tb, count, v, lds_rec[(uint32_t)(tb + (j & (kB - 1)) + 1 - chunk0) * ROW + in_at]);
+    } else {
+      batch_run(core_tag, tb, count, v, lds_raw[(uint32_t)(tb + (j & (kB - 1)) + 1 - raw0) * ROW + in_at]);
+    }
+  };
 
   auto input_at = [&](int32_t t) -> uint32_t { return lds_raw[(uint32_t)(t - raw0) * ROW + in_at]; };
   auto general = [&](int32_t t) {
@@ -995,6 +1052,56 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
     if ((rel & (kB - 1)) == kB - 1) batch(std::false_type(), t - (kB - 1), kB);
   };
   int32_t t = p.f0;
+  if constexpr (kSplit) {
+    if (consumer) {
+      // The consumer wave: per core block, the saves of its eight steps (checksum, first-seen
+      // compare in the same step, the seven stores) and its batch, from the producer's hand-off.
+      block_barrier();  // the producer's publish()
+      const int32_t nb = lds_ctl[0];
+      t = lds_ctl[1];
+      if (nb == 0) return;
+      // ring and trace slots as the one-wave kernel has them at step t (t - f0 a multiple of 8)
+      sr = __builtin_amdgcn_readfirstlane((g0 + 1 + (t - p.f0)) % R);
+      sb = __builtin_amdgcn_readfirstlane(p.trace_cap ? (p.f0 - (CD - 1) + (t - p.f0)) % p.trace_cap : 0);
+      const uint32_t hand_first = (uint32_t)(base + (CD - 1) * Pp + pl);  // role cd-1's lane: the stash
+      for (int32_t k = 0; k < nb; ++k, t += kB) {
+        block_barrier();  // block k's hand-off buffer is written
+        const uint8_t* hb = lds_hand + (k & 1) * (kB * kHSlot);
+        uint32_t v[kB][5];
+#pragma unroll
+        for (int u = 0; u < kB; u++) {
+          const uint4 a = *reinterpret_cast<const uint4*>(hb + u * kHSlot + wl * 16);
+          v[u][0] = a.x, v[u][1] = a.y, v[u][2] = a.z, v[u][3] = a.w;
+          v[u][4] = *reinterpret_cast<const uint32_t*>(hb + u * kHSlot + kWave * 16 + wl * 4);
+        }
+        uint32_t bv[5];
+        {
+          const uint8_t* st = hb + (j & (kB - 1)) * kHSlot;
+          const uint4 a = *reinterpret_cast<const uint4*>(st + hand_first * 16);
+          bv[0] = a.x, bv[1] = a.y, bv[2] = a.z, bv[3] = a.w;
+          bv[4] = *reinterpret_cast<const uint32_t*>(st + kWave * 16 + hand_first * 4);
+        }
+        const uint4 brec = lds_hrec[(k & 1) * kWave + wl];
+#pragma unroll
+        for (int u = 0; u < kB; u++) {
+          const uint32_t frame1 = (uint32_t)(t + u - CD + 1);
+          const uint32_t ck = cell_checksum(v[u], frame1);
+          acc |= ck ^ first_seen(ck);
+          store_cell(v[u], frame1, ck, (uint32_t)sr);
+          sr = sr + 1 == R ? 0 : sr + 1;
+        }
+        batch_run(std::true_type(), t, kB, bv, brec);
+      }
+      bad |= __ballot(acc != 0) & cmp_lanes;
+      if (bad && wl == __builtin_ctzll(bad)) atomicCAS(p.fail_f0, -1, p.f0);
+      // Every store of this wave has reached memory before the producer passes the last barrier:
+      // its last steps write ring cells (steps t and t + R share one), trace cells and cur after
+      // them, as the one-wave kernel's program order has it.
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+      block_barrier();
+      return;
+    }
+  }
   // lean launches of whole 8-step blocks run their first and last steps as edge steps (the core
   // step's code, already warm in the instruction cache, with the general step's bookkeeping);
   // others take the general step there
@@ -1019,22 +1126,52 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v5_kernel(PipeParams
     // core blocks of 8 steps + their batch, aligned to the batch grid
     for (; t < core_end && ((t - p.f0) & (kB - 1)) != 0; ++t) general(t);
   }
-  if (t + kB <= core_end) {
+  const int32_t n_core = t + kB <= core_end ? (core_end - t) / kB : 0;
+  if constexpr (kSplit) {
+    // The steps so far have stored ring and trace cells that the consumer's steps store again
+    // (steps t and t + R share a ring cell): those stores have reached memory before the consumer,
+    // which issues its first store after this barrier, can pass it.
+    if (n_core > 0) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    publish(n_core, t);
+  }
+  if (n_core > 0) {
     bad |= __ballot(pend_ck != pend_first) & pend_lanes;
     pend_ck = pend_first = 0;
     pend_lanes = cmp_lanes;
     glibc_sincosf_domain_raw(__builtin_bit_cast(float, w[4]), &sc_s, &sc_c, &sc_qs, &sc_qc);
-    for (; t + kB <= core_end; t += kB) {
+    // the producer is the longer dependent chain: it issues first when both waves of a SIMD are
+    // ready, the consumer fills the cycles it leaves (measured, DESIGN.md §5: 0.154 -> 0.146 ms)
+    if constexpr (kSplit) __builtin_amdgcn_s_setprio(1);
+    for (int32_t k = 0; k < n_core; ++k, t += kB) {
       if (((t - p.f0) & (kStage5 - 1)) == 0) stage(t);
       const uint32_t ip = (uint32_t)(t - chunk0) * ROW + in_at;
       uint4 in[kB];
 #pragma unroll
       for (int u = 0; u < kB; u++) in[u] = lds_rec[ip + u * ROW];
+      if constexpr (kSplit) {
+        // Block k goes into hand-off buffer k & 1, which the consumer read for block k - 2 before
+        // it arrived at the barrier this wave passed last; the barrier below hands block k over.
+        const uint32_t hb = (uint32_t)(k & 1) * (kB * kHSlot);
+        lds_hrec[(k & 1) * kWave + wl] = lds_rec[ip + (uint32_t)((j & (kB - 1)) + 1) * ROW];
 #pragma unroll
-      for (int u = 0; u < kB; u++) step(std::true_type(), t + u, in[u], (uint32_t)(u * kSlot));
-      batch(std::true_type(), t, kB);
+        for (int u = 0; u < kB; u++) step(std::true_type(), t + u, in[u], hb + (uint32_t)(u * kHSlot));
+        sb = sb + sb_step;
+        sb = sb >= tcap ? sb - tcap : sb;
+        block_barrier();
+      } else {
+#pragma unroll
+        for (int u = 0; u < kB; u++) step(std::true_type(), t + u, in[u], (uint32_t)(u * kSlot));
+        batch(std::true_type(), t, kB);
+      }
     }
-    bad |= __ballot(acc != 0) & cmp_lanes;
+    if constexpr (kSplit) {
+      __builtin_amdgcn_s_setprio(0);
+      sr = (sr + n_core * kB) % R;
+      // the consumer's last store has reached memory (it drains them before this barrier)
+      block_barrier();
+    } else {
+      bad |= __ballot(acc != 0) & cmp_lanes;
+    }
   }
   if (edge_ok) {
     edge_block(t, t_end - t);  // the last cd - 1 steps and their batch
@@ -1392,10 +1529,10 @@ static int launch_pipelined(ggrs_engine_t* e, int32_t f0, int32_t n) {
   return launch_timed(e, [&] {
     if (kernel == 5) {
       switch (e->cfg.num_players) {
-        case 1: synctest_pipelined_v5_kernel<1><<<grid, kWave, 0, e->stream>>>(p); break;
-        case 2: synctest_pipelined_v5_kernel<2><<<grid, kWave, 0, e->stream>>>(p); break;
-        case 3: synctest_pipelined_v5_kernel<3><<<grid, kWave, 0, e->stream>>>(p); break;
-        default: synctest_pipelined_v5_kernel<4><<<grid, kWave, 0, e->stream>>>(p); break;
+        case 1: synctest_pipelined_v5_kernel<1, false><<<grid, kWave, 0, e->stream>>>(p); break;
+        case 2: synctest_pipelined_v5_kernel<2, true><<<grid, 2 * kWave, 0, e->stream>>>(p); break;
+        case 3: synctest_pipelined_v5_kernel<3, false><<<grid, kWave, 0, e->stream>>>(p); break;
+        default: synctest_pipelined_v5_kernel<4, false><<<grid, kWave, 0, e->stream>>>(p); break;
       }
       return;
     }
