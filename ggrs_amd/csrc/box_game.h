@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "glibc_sincosf.h"
+#include "host_device.h"
 
 #pragma clang fp contract(off)
 
@@ -30,8 +31,7 @@ constexpr float kPi = 3.14159265358979323846f;   // std::f32::consts::PI
 constexpr float kTwoPi = 2.0f * kPi;             // 2.0 * PI evaluated in f32
 constexpr uint32_t kInputUp = 1u, kInputDown = 2u, kInputLeft = 4u, kInputRight = 8u;
 
-// Number of 32-bit fields of the SoA state: frame + (x, y, vx, vy, rot) per player.
-__host__ __device__ constexpr int state_fields(int p) { return 1 + 5 * p; }
+// (state_fields(p), the number of 32-bit fields of the SoA state, is in host_device.h)
 // bincode size of State (fixint LE): i32 + u64 + 3 * (u64 len) + 20 * P.
 __host__ __device__ constexpr int bincode_bytes(int p) { return 36 + 20 * p; }
 

@@ -1,4 +1,5 @@
-// common.h -- helpers shared by the engine translation units (engine.hip, branch.hip).
+// common.h -- helpers shared by every HIP translation unit (engine.hip, requests.hip, branch.hip, particles.hip,
+// p2p.hip, p2p_sched.hip, codec.hip, spectator.hip; through engine.h and p2p_engine.h too).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,6 +8,7 @@
 
 #include "ggrs_amd.h"
 #include "box_game.h"
+#include "host_device.h"
 
 #pragma clang fp contract(off)
 
@@ -20,8 +22,6 @@ int set_error(int code, const char* fmt, ...);
     hipError_t e_ = (expr);                                                                      \
     if (e_ != hipSuccess) return ::ggrs::set_error(GGRS_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
-
-constexpr int kWave = 64;
 
 // Device time of a span of fused launches (ggrs_*_timing_reset .. _read): one HIP event pair on
 // the engine's stream brackets the whole span, so the timed path records no per-launch events
@@ -101,9 +101,6 @@ __device__ inline int64_t xcd_block(int64_t i, int64_t n) {
   const int64_t q = n / kXcds, r = n % kXcds, x = i % kXcds, k = i / kXcds;
   return x * q + (x < r ? x : r) + k;
 }
-
-inline int padded_players(int p) { return p <= 1 ? 1 : (p == 2 ? 2 : 4); }
-inline int64_t grid_of(int64_t n, int64_t block) { return (n + block - 1) / block; }
 
 template <int P>
 struct InputWord;
@@ -190,6 +187,7 @@ __global__ void pack_inputs_kernel(const uint8_t* src, uint8_t* dst, int64_t L, 
   for (int k = 0; k < Pp; k++) dst[(q * L + lane) * Pp + k] = k < P ? src[i * P + k] : 0;
 }
 
+// Run-time values as template arguments, one dispatcher per axis: f gets an integral_constant.
 template <typename F>
 inline void dispatch_players(int p, F&& f) {
   switch (p) {
@@ -198,6 +196,21 @@ inline void dispatch_players(int p, F&& f) {
     case 3: f(std::integral_constant<int, 3>()); break;
     default: f(std::integral_constant<int, 4>()); break;
   }
+}
+// kLocal: the local mask as a compile-time constant for two players with one of them local (1 or
+// 2), else -1 (the kernel reads the mask from its parameters)
+template <int P, typename F>
+inline void dispatch_local(uint32_t local_mask, F&& f) {
+  if constexpr (P == 2) {
+    if (local_mask == 1u) return f(std::integral_constant<int, 1>());
+    if (local_mask == 2u) return f(std::integral_constant<int, 2>());
+  }
+  f(std::integral_constant<int, -1>());
+}
+template <typename F>
+inline void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type());
+  else f(std::false_type());
 }
 
 // A pointer held in vector registers: the kernel's uniform values exceed the scalar register file

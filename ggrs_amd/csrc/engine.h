@@ -73,9 +73,7 @@ struct ggrs_engine {
   int32_t corrupt_lane = -1, corrupt_frame = -1;
   // timing: between ggrs_timing_reset and ggrs_timing_read one event pair brackets every fused
   // launch of the span (no per-launch events in the timed path)
-  hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-  bool collecting = false, span_open = false, span_stopped = false;
-  int32_t span_launches = 0;
+  ggrs::SpanTimer timer;
   float last_span_ms = -1.0f;
   int32_t last_span_launches = 0;
   // per-lane request lists
@@ -97,13 +95,10 @@ void lane_server_release(ggrs_engine* e);
 // Counts one fused launch of a timed span; the span's first launch records its begin event.
 template <typename K>
 inline int launch_timed(ggrs_engine* e, K&& launch) {
-  if (e->collecting && !e->span_open) {
-    HIP_TRY(hipEventRecord(e->ev_begin, e->stream));
-    e->span_open = true;
-  }
+  if (int rc = e->timer.before(e->stream)) return rc;
   launch();
   HIP_TRY(hipGetLastError());
-  if (e->collecting) e->span_launches++;
+  e->timer.count();
   return GGRS_OK;
 }
 

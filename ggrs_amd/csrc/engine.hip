@@ -1309,8 +1309,7 @@ int ggrs_engine_destroy(ggrs_engine_t* e) {
   if (e->batch.base) (void)hipHostFree(e->batch.base);
   if (e->server.mem) (void)hipHostFree(e->server.mem);
   if (e->server.dev) (void)hipFree(e->server.dev);
-  if (e->ev_begin) (void)hipEventDestroy(e->ev_begin);
-  if (e->ev_end) (void)hipEventDestroy(e->ev_end);
+  e->timer.destroy();
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
   return GGRS_OK;
@@ -1355,8 +1354,7 @@ int ggrs_engine_create(const ggrs_config_t* cfg, ggrs_engine_t** out) {
   const int64_t L = c.num_lanes;
   CTRY(hipSetDevice(c.device));
   CTRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  CTRY(hipEventCreate(&e->ev_begin));
-  CTRY(hipEventCreate(&e->ev_end));
+  if (e->timer.create()) return fail(GGRS_E_HIP);
   {
     auto up16 = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_cur = up16(sizeof(uint32_t) * e->F * L);
@@ -1894,46 +1892,23 @@ int ggrs_timing_reset(ggrs_engine_t* e) {
   if (!e) return set_error(GGRS_E_INVALID, "null engine");
   HIP_TRY(hipSetDevice(e->cfg.device));
   if (int rc = lane_server_stop(e)) return rc;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  e->collecting = true;
-  e->span_open = false;
-  e->span_stopped = false;
-  e->span_launches = 0;
-  return GGRS_OK;
+  return e->timer.reset(e->stream);
 }
 
 int ggrs_timing_stop(ggrs_engine_t* e) {
   if (!e) return set_error(GGRS_E_INVALID, "null engine");
   HIP_TRY(hipSetDevice(e->cfg.device));
   if (int rc = lane_server_stop(e)) return rc;
-  if (e->span_open && !e->span_stopped) {
-    HIP_TRY(hipEventRecord(e->ev_end, e->stream));
-    e->span_stopped = true;
-  }
-  e->collecting = false;
-  return GGRS_OK;
+  return e->timer.stop(e->stream);
 }
 
 int ggrs_timing_read(ggrs_engine_t* e, float* total_ms, int32_t* launches) {
   if (!e || !total_ms || !launches) return set_error(GGRS_E_INVALID, "null argument");
   HIP_TRY(hipSetDevice(e->cfg.device));
   if (int rc = lane_server_stop(e)) return rc;
-  float ms = 0.0f;
-  if (e->span_open) {
-    if (!e->span_stopped) HIP_TRY(hipEventRecord(e->ev_end, e->stream));
-    HIP_TRY(hipEventSynchronize(e->ev_end));
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev_begin, e->ev_end));
-  } else {
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  *total_ms = ms;
-  *launches = e->span_launches;
-  e->last_span_ms = ms;
-  e->last_span_launches = e->span_launches;
-  e->collecting = false;
-  e->span_open = false;
-  e->span_stopped = false;
-  e->span_launches = 0;
+  if (int rc = e->timer.read(e->stream, total_ms, launches)) return rc;
+  e->last_span_ms = *total_ms;
+  e->last_span_launches = *launches;
   return GGRS_OK;
 }
 

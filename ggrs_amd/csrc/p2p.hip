@@ -40,6 +40,7 @@
 
 #include "common.h"
 #include "p2p_engine.h"
+#include "p2p_plan.h"
 
 #pragma clang fp contract(off)
 
@@ -84,9 +85,6 @@ struct RemoteQueues {
   int32_t last_req[P];    // last_requested_frame
 };
 
-// dwords of one ring cell: the state's F fields and the checksum, padded to whole 16-byte pieces
-__host__ __device__ constexpr int cell_dwords(int p) { return (state_fields(p) + 1 + 3) & ~3; }
-
 template <int P>
 __device__ inline uint4* ring_cell(const P2PParams& p, int32_t slot, int64_t sess) {
   return reinterpret_cast<uint4*>(p.ring + ((int64_t)sess * p.R + slot) * cell_dwords(P));
@@ -126,9 +124,8 @@ __device__ inline void save_cell(const P2PParams& p, const BoxState<P>& s, int32
 }
 
 // Input rows as the calls read them: from global memory, or (staged kernel) from the block's LDS
-// copy of rows [lo, lo + kP2PRows) -- one LDS byte read instead of a dependent global load.
-constexpr int kP2PRows = 64;
-constexpr int kP2PBlock = 256;
+// copy of rows [lo, lo + kP2PRows) -- one LDS byte read instead of a dependent global load
+// (kP2PRows, kP2PBlock: p2p_plan.h).
 
 template <int P>
 struct GlobalRows {
@@ -372,17 +369,7 @@ __global__ __launch_bounds__(kP2PBlock) void p2p_kernel(P2PParams p) {
 // count (calls + replays) of a stage.  Same Loads, Saves, AdvanceFrames and InputQueue updates per
 // session, in the same order, as p2p_kernel.  One wave per block; input rows staged per stage of
 // calls as in the staged form (rows [stage start - back, stage end)), all lanes meeting at the
-// stage end.
-constexpr int kFlatBlock = 64;
-// rows per stage: a wave's steps in a stage are its slowest session's, so fewer, longer stages
-// cost less (128 rows: one stage per 64-call launch at back = 6)
-constexpr int kFlatRows = 128;
-// with the LDS ring: 12 KB of rows (96 at two players: a 64-call launch is one stage) beside a
-// ring of at most 28 KB per block, four blocks per CU in 160 KB
-template <int P>
-constexpr int flat_rows_lds() {
-  return 12 * 1024 / (kFlatBlock * (P <= 1 ? 1 : (P == 2 ? 2 : 4)));
-}
+// stage end.  (kFlatBlock, kFlatRows, flat_rows_lds: p2p_plan.h)
 
 template <int P>
 struct LdsRowsFlat {
@@ -1146,7 +1133,7 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_sparse_kernel(P2PParams 
 // launches (no desync detection, trace or debug flip, never sparse saving), f0 >= D (the first D
 // calls run on the flat kernel), K * Pp <= 64.
 constexpr uint32_t kChainOob = 0x40000000u;  // past every descriptor's range: a lane that never stores
-constexpr int kChainLdsRows = 16 * 1024;      // bytes of staged input rows per block
+// (kChainLdsRows, kStashEntry, kChainFastLds: p2p_plan.h)
 
 //   kB (2 <= D <= 8): roles 0 .. D - 1 only, as the v5 SyncTest kernel does: role D -- each chain's
 // last AdvanceFrame, the call's own frame, whose state no other role consumes -- leaves the
@@ -1154,7 +1141,6 @@ constexpr int kChainLdsRows = 16 * 1024;      // bytes of staged input rows per 
 // batch sub-step advances the D stashed states (role lane j takes step j's).  D x Pp lanes per
 // session instead of (D + 1) x Pp (config 2's P2P shape, D = 8 and two players: four sessions
 // per wave instead of three), one extra step's work per D steps.
-constexpr int kStashEntry = 32;  // bytes per (session, player) entry of a stash slot: 5 fields
 
 //   kD = 8 at two players (config 2's P2P shape; the host picks it when remote_latency is 8): D
 // is a compile-time constant and a session's 16 lanes are one DPP row, so the lean steps run as
@@ -1162,7 +1148,6 @@ constexpr int kStashEntry = 32;  // bytes per (session, player) entry of a stash
 // every input byte decoded once per launch into an InputRec in LDS, and each step's sin/cos
 // computed one step ahead, inside the previous step, from the rotated rot.  Same operations on
 // the same values as the general step: the same bits.
-constexpr int kChainFastLds = 40 * 1024;  // the kD form's LDS budget per block (four blocks per CU)
 
 template <int P, bool kB, int kD = 0>
 __global__ __launch_bounds__(kWave) void p2p_chains_kernel(P2PParams p, int32_t spw) {
@@ -1678,6 +1663,82 @@ void lockstep_program(ggrs_p2p_engine* e, int32_t f0, int32_t n, std::vector<int
   }
 }
 
+// Replays the lockstep calls f0 .. f0+n-1 on the host and puts their program in e->ls_prog.
+int lockstep_upload(ggrs_p2p_engine* e, int32_t f0, int32_t n) {
+  std::vector<int32_t> prog;
+  lockstep_program(e, f0, n, prog);
+  if (n > e->ls_prog_cap) {
+    if (e->ls_prog) HIP_TRY(hipFree(e->ls_prog));
+    e->ls_prog = nullptr;
+    e->ls_prog_cap = 0;
+    HIP_TRY(hipMalloc(&e->ls_prog, sizeof(int32_t) * 2 * (size_t)n));
+    e->ls_prog_cap = n;
+  }
+  HIP_TRY(hipMemcpyAsync(e->ls_prog, prog.data(), sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));  // prog is host memory that goes out of scope
+  return GGRS_OK;
+}
+
+// One launch function per kernel family: the plan's selectors become template arguments.  The
+// sparse flat kernel is not specialised on the local mask, the compile-time chains form exists
+// for two players only.
+template <int P>
+void launch_flat(const P2PLaunch& L, const P2PParams& p, hipStream_t stream) {
+  dispatch_bool(L.lds_ring, [&](auto LR) {
+    dispatch_bool(L.plain, [&](auto PL) {
+      constexpr bool kPl = decltype(PL)::value, kL = decltype(LR)::value;
+      if (L.sparse) {
+        p2p_flat_kernel<P, -1, kPl, true, kL><<<L.grid, L.block, L.lds, stream>>>(p);
+        return;
+      }
+      dispatch_local<P>(p.local_mask, [&](auto LC) {
+        p2p_flat_kernel<P, decltype(LC)::value, kPl, false, kL><<<L.grid, L.block, L.lds, stream>>>(p);
+      });
+    });
+  });
+}
+
+template <int P>
+void launch_chains(const P2PLaunch& L, const P2PParams& p, hipStream_t stream) {
+  if constexpr (P == 2) {
+    if (L.chain_fast) {
+      p2p_chains_kernel<P, true, 8><<<L.grid, L.block, L.lds, stream>>>(p, L.spw);
+      return;
+    }
+  }
+  dispatch_bool(L.chain_batch, [&](auto CB) {
+    p2p_chains_kernel<P, decltype(CB)::value><<<L.grid, L.block, L.lds, stream>>>(p, L.spw);
+  });
+}
+
+// (The order of the cases is the order in which the kernels are instantiated, and the compiler's
+// inlining of the device functions they share depends on it -- p2p_kernel<2, false> came out
+// different with p2p_kernel first -- so a reordering is a change of device code.)
+template <int P>
+void launch_p2p(const P2PLaunch& L, const P2PParams& p, const int32_t* ls_prog, hipStream_t stream) {
+  switch (L.kernel) {
+    case P2PKernel::kLockstep: p2p_lockstep_kernel<P><<<L.grid, L.block, 0, stream>>>(p, ls_prog); break;
+    case P2PKernel::kChains: launch_chains<P>(L, p, stream); break;
+    case P2PKernel::kCanonSparse:
+      dispatch_local<P>(p.local_mask, [&](auto LC) {
+        p2p_canon_sparse_kernel<P, decltype(LC)::value><<<L.grid, L.block, L.lds, stream>>>(p);
+      });
+      break;
+    case P2PKernel::kCanon:
+      dispatch_local<P>(p.local_mask, [&](auto LC) {
+        p2p_canon_kernel<P, decltype(LC)::value><<<L.grid, L.block, L.lds, stream>>>(p);
+      });
+      break;
+    case P2PKernel::kFlat: launch_flat<P>(L, p, stream); break;
+    case P2PKernel::kStaged:
+    case P2PKernel::kUnstaged:
+      dispatch_bool(L.kernel == P2PKernel::kStaged, [&](auto ST) {
+        p2p_kernel<P, decltype(ST)::value><<<L.grid, L.block, 0, stream>>>(p);
+      });
+      break;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1842,176 +1903,43 @@ int ggrs_p2p_advance_frames(ggrs_p2p_engine_t* e, int32_t n) {
   // rows the calls read must still be in the ring: rows >= oldest_row(f0) up to f0 + n - 1
   if ((int64_t)p.f0 + n - 1 - oldest_row(e, p.f0) >= e->cap)
     return set_error(GGRS_E_INVALID, "advance of %d frames reads more input rows than input_capacity (%d)", n, e->cap);
-  if (e->cfg.max_prediction == 0) {  // lockstep mode
-    std::vector<int32_t> prog;
-    lockstep_program(e, p.f0, n, prog);
-    if (n > e->ls_prog_cap) {
-      if (e->ls_prog) HIP_TRY(hipFree(e->ls_prog));
-      e->ls_prog = nullptr;
-      e->ls_prog_cap = 0;
-      HIP_TRY(hipMalloc(&e->ls_prog, sizeof(int32_t) * 2 * (size_t)n));
-      e->ls_prog_cap = n;
-    }
-    HIP_TRY(hipMemcpyAsync(e->ls_prog, prog.data(), sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));  // prog is host memory that goes out of scope
+  P2PPlanIn in{};
+  in.sessions = p.S;
+  in.players = e->cfg.num_players;
+  in.local_mask = p.local_mask;
+  in.remote_latency = p.D;
+  in.input_delay = p.delay;
+  in.max_prediction = e->cfg.max_prediction;
+  in.R = e->R;
+  in.cap = e->cap;
+  in.predictor = p.predictor;
+  in.sparse = e->sparse != 0;
+  in.trace = e->trace != nullptr;
+  in.desync = e->desync_interval != 0;
+  in.dbg_armed = e->dbg_sess >= 0;
+  in.dbg_ever = e->dbg_ever;
+  in.form = e->form;
+  in.num_cus = e->num_cus;
+  in.f0 = p.f0;
+  in.left = n;
+  // a long run takes several launches (p2p_plan.h); an error in a later one leaves the earlier ones run
+  while (in.left > 0) {
+    P2PLaunch L;
+    const char* msg = nullptr;
+    if (int rc = p2p_plan_next(in, &L, &msg)) return set_error(rc, "%s", msg);
+    p.f0 = in.f0;
+    p.n = L.n;
+    if (L.kernel == P2PKernel::kLockstep)
+      if (int rc = lockstep_upload(e, p.f0, L.n)) return rc;
     int rc = p2p_launch_timed(e, [&] {
-      dispatch_players(e->cfg.num_players, [&](auto PC) {
-        constexpr int P = decltype(PC)::value;
-        p2p_lockstep_kernel<P><<<grid_of(p.S, 256), 256, 0, e->stream>>>(p, e->ls_prog);
-      });
+      dispatch_players(in.players, [&](auto PC) { launch_p2p<decltype(PC)::value>(L, p, e->ls_prog, e->stream); });
     });
     if (rc) return rc;
-    e->current_frame += n;
-    return GGRS_OK;
+    e->current_frame += L.n;
+    in.f0 += L.n;
+    in.left -= L.n;
+    in.row_left = L.row_left;
   }
-  // the chains form: forced (form 4), or by default when the flat kernel's one thread per session
-  // would leave most SIMDs idle
-  const int P = e->cfg.num_players;
-  // the chains form's lanes per session: D roles + the batch for 2 <= D <= 8, else D + 1 roles
-  const bool chain_batch = p.D >= 2 && p.D <= 8;
-  const int G = (chain_batch ? p.D : p.D + 1) * padded_players(P);
-  // plain history: the session's states are the canonical ones the remote inputs determine (the
-  // canonical flat kernel also keeps the desync history; the chains form does not)
-  const bool plain_hist = !e->sparse && !p.trace && !e->dbg_ever;
-  const bool chains_ok = plain_hist && e->desync_interval == 0 && G <= kWave &&
-                         (uint64_t)p.S * e->R * cell_dwords(P) * 4 < ((uint64_t)1 << 30);
-  const bool chains = chains_ok && (e->form == 4 || (e->form == 0 && grid_of(p.S, kFlatBlock) <= e->num_cus));
-  if (e->form == 4 && !chains_ok)
-    return set_error(GGRS_E_STATE, "the chains form needs plain launches (no desync detection, trace, debug flip or "
-                                   "sparse saving), (remote_latency + 1) x padded players <= 64 lanes and a ring < 1 GiB");
-  // the canonical flat kernel needs the same plain history and the remote inputs flowing (f0 >= D)
-  const bool canon_ok = plain_hist && (e->form == 0 || e->form == 6);
-  // and its sparse-saving form the same launches with sparse saving on
-  const bool canon_sparse_ok = e->sparse && !p.trace && !e->dbg_ever && (e->form == 0 || e->form == 6);
-  if ((chains || canon_ok || canon_sparse_ok) && p.f0 < p.D) {  // the first D calls (no remote input yet): general flat
-    const int32_t m = std::min(n, p.D - p.f0);
-    const int32_t form = e->form;
-    e->form = 5;
-    int rc = ggrs_p2p_advance_frames(e, m);
-    e->form = form;
-    if (rc || m == n) return rc;
-    return ggrs_p2p_advance_frames(e, n - m);
-  }
-  if (chains) {
-    const int spw = kWave / G;
-    const int row_bytes = spw * padded_players(P);
-    // a launch's rows (f0 - 2D - delay .. f0 + n - 1) must fit the block's LDS: longer runs split
-    const int32_t max_n = kChainLdsRows / row_bytes - 2 * p.D - p.delay;
-    if (max_n < 1) return set_error(GGRS_E_INVALID, "remote_latency / input_delay too large for the chains form");
-    if (n > max_n) {
-      int rc = ggrs_p2p_advance_frames(e, max_n);
-      if (rc) return rc;
-      return ggrs_p2p_advance_frames(e, n - max_n);
-    }
-    // config 2's P2P shape (latency 8, two players): the compile-time form, whose decoded input
-    // records cap a launch's rows by its LDS budget
-    const size_t fast_fixed = (size_t)2 * 8 * row_bytes * kStashEntry + 16 + 16;  // stash, alignment, input-0 record
-    const int32_t fast_n = (int32_t)((kChainFastLds - fast_fixed) / ((size_t)row_bytes * 17)) - 2 * p.D - p.delay;
-    // (an input delay so long that no call fits the budget: the general form)
-    const bool fast = chain_batch && p.D == 8 && P == 2 && fast_n >= 1;
-    if (fast) {
-      if (n > fast_n) {
-        int rc = ggrs_p2p_advance_frames(e, fast_n);
-        if (rc) return rc;
-        return ggrs_p2p_advance_frames(e, n - fast_n);
-      }
-    }
-    size_t lds = (size_t)(n + 2 * p.D + p.delay) * row_bytes;
-    const size_t n_entries = lds;
-    if (chain_batch) lds = ((lds + 15) & ~(size_t)15) + (size_t)(p.D + 1) * kWave * kStashEntry;
-    if (fast)  // rows, the stash's 2D slots of row_bytes entries, the input records
-      lds = ((n_entries + 15) & ~(size_t)15) + (size_t)2 * p.D * row_bytes * kStashEntry + (n_entries + 1) * 16;
-    int rc = p2p_launch_timed(e, [&] {
-      dispatch_players(P, [&](auto PC) {
-        constexpr int PP = decltype(PC)::value;
-        if constexpr (PP == 2) {
-          if (fast) {
-            p2p_chains_kernel<PP, true, 8><<<(unsigned)grid_of(p.S, spw), kWave, lds, e->stream>>>(p, spw);
-            return;
-          }
-        }
-        if (chain_batch) p2p_chains_kernel<PP, true><<<(unsigned)grid_of(p.S, spw), kWave, lds, e->stream>>>(p, spw);
-        else p2p_chains_kernel<PP, false><<<(unsigned)grid_of(p.S, spw), kWave, lds, e->stream>>>(p, spw);
-      });
-    });
-    if (rc) return rc;
-    e->current_frame += n;
-    return GGRS_OK;
-  }
-  int rc = p2p_launch_timed(e, [&] {
-    // stage input rows in LDS unless a call reaches further back than a stage holds
-    const int32_t back = (e->sparse ? e->R - 1 : p.D) + p.delay;
-    const bool staged = back + 1 <= kP2PRows - 1 && e->form != 1;
-    // the flat form by default: with the session-major ring its saves stay whole cache lines
-    // whatever frame each lane is at (1.82e10 vs lockstep 1.26e10 session-frames/s at 65,536
-    // sessions, 1.98e10 vs 1.89e10 at 131,072; with the frame-major ring of round 1 the flat
-    // form's partial lines went out to HBM 3.5x over -- DESIGN.md section 5)
-    const bool flat = staged && (e->form == 0 || e->form == 3 || e->form == 5 || e->form == 6);
-    dispatch_players(e->cfg.num_players, [&](auto PC) {
-      constexpr int P = decltype(PC)::value;
-      if (flat) {
-        const dim3 grid((unsigned)grid_of(p.S, kFlatBlock));
-        // the LDS ring when a stage of rows holds a call's reach and the block's rings fit: 28 KB
-        // (four blocks, one per SIMD, in a CU's 160 KB beside 12 KB of rows each), or more when the
-        // grid puts fewer blocks on each CU (config 2's P2P shape: 4096 sessions = 64 blocks, R = 10:
-        // 30 KB of rings)
-        const size_t ring_lds = (size_t)e->R * (cell_dwords(P) / 4) * kFlatBlock * 16;
-        const size_t rows_lds = (size_t)flat_rows_lds<P>() * kFlatBlock * (P <= 1 ? 1 : (P == 2 ? 2 : 4));
-        const int64_t per_cu = (grid.x + e->num_cus - 1) / e->num_cus;
-        const bool fits = ring_lds <= 28 * 1024 ||
-                          (ring_lds + rows_lds <= 64 * 1024 && per_cu * (int64_t)(ring_lds + rows_lds) <= 160 * 1024);
-        const bool lds = e->form != 3 && fits && back + 1 <= flat_rows_lds<P>() - 1;
-        auto go = [&](auto plain_tag, auto lds_tag) {
-          constexpr bool kPl = decltype(plain_tag)::value;
-          constexpr bool kL = decltype(lds_tag)::value;
-          const size_t shm = kL ? ring_lds : 0;
-          if (e->sparse) {
-            p2p_flat_kernel<P, -1, kPl, true, kL><<<grid, kFlatBlock, shm, e->stream>>>(p);
-          } else if constexpr (P == 2) {
-            if (p.local_mask == 1u) p2p_flat_kernel<P, 1, kPl, false, kL><<<grid, kFlatBlock, shm, e->stream>>>(p);
-            else if (p.local_mask == 2u) p2p_flat_kernel<P, 2, kPl, false, kL><<<grid, kFlatBlock, shm, e->stream>>>(p);
-            else p2p_flat_kernel<P, -1, kPl, false, kL><<<grid, kFlatBlock, shm, e->stream>>>(p);
-          } else {
-            p2p_flat_kernel<P, -1, kPl, false, kL><<<grid, kFlatBlock, shm, e->stream>>>(p);
-          }
-        };
-        const bool plain = p.desync_interval == 0 && !p.trace && p.dbg_sess < 0;
-        if (lds && canon_sparse_ok) {  // the canonical flat kernel with sparse saving (f0 >= D here)
-          const size_t shm = ring_lds;
-          if constexpr (P == 2) {
-            if (p.local_mask == 1u) p2p_canon_sparse_kernel<P, 1><<<grid, kFlatBlock, shm, e->stream>>>(p);
-            else if (p.local_mask == 2u) p2p_canon_sparse_kernel<P, 2><<<grid, kFlatBlock, shm, e->stream>>>(p);
-            else p2p_canon_sparse_kernel<P, -1><<<grid, kFlatBlock, shm, e->stream>>>(p);
-          } else {
-            p2p_canon_sparse_kernel<P, -1><<<grid, kFlatBlock, shm, e->stream>>>(p);
-          }
-          return;
-        }
-        if (lds && canon_ok) {  // the canonical flat kernel (f0 >= D here)
-          const size_t shm = ring_lds;
-          if constexpr (P == 2) {
-            if (p.local_mask == 1u) p2p_canon_kernel<P, 1><<<grid, kFlatBlock, shm, e->stream>>>(p);
-            else if (p.local_mask == 2u) p2p_canon_kernel<P, 2><<<grid, kFlatBlock, shm, e->stream>>>(p);
-            else p2p_canon_kernel<P, -1><<<grid, kFlatBlock, shm, e->stream>>>(p);
-          } else {
-            p2p_canon_kernel<P, -1><<<grid, kFlatBlock, shm, e->stream>>>(p);
-          }
-          return;
-        }
-        if (lds) {
-          if (plain) go(std::true_type(), std::true_type());
-          else go(std::false_type(), std::true_type());
-        } else {
-          if (plain) go(std::true_type(), std::false_type());
-          else go(std::false_type(), std::false_type());
-        }
-      }
-      else if (staged) p2p_kernel<P, true><<<grid_of(p.S, kP2PBlock), kP2PBlock, 0, e->stream>>>(p);
-      else p2p_kernel<P, false><<<grid_of(p.S, kP2PBlock), kP2PBlock, 0, e->stream>>>(p);
-    });
-  });
-  if (rc) return rc;
-  e->current_frame += n;
   return GGRS_OK;
 }
 
@@ -2059,10 +1987,13 @@ int ggrs_p2p_set_sparse_saving(ggrs_p2p_engine_t* e, int32_t on) {
 
 int ggrs_p2p_set_unstaged(ggrs_p2p_engine_t* e, int32_t form) {
   if (!e) return set_error(GGRS_E_INVALID, "null engine");
-  if (form < 0 || form > 6)
-    return set_error(GGRS_E_INVALID, "kernel form %d (0 default, 1 unstaged, 2 lockstep, 3 flat HBM rings, 4 chains, "
-                                     "5 flat LDS rings with the queue bookkeeping, 6 canonical flat)", form);
-  e->form = form;
+  if (form < 0 || form >= kP2PFormCount) {
+    std::string forms;  // "0 default, 1 unstaged, ..."
+    for (const P2PFormInfo& f : kP2PForms)
+      forms += (forms.empty() ? "" : ", ") + std::to_string((int)f.form) + " " + f.what;
+    return set_error(GGRS_E_INVALID, "kernel form %d (%s)", form, forms.c_str());
+  }
+  e->form = (P2PForm)form;
   return GGRS_OK;
 }
 

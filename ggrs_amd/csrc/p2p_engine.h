@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "common.h"
+#include "p2p_plan.h"
 
 struct ggrs_p2p_engine {
   ggrs_p2p_config_t cfg{};
@@ -33,9 +34,7 @@ struct ggrs_p2p_engine {
   int64_t dbg_sess = -1;
   int32_t dbg_frame = -1;
   int32_t sparse = 0;
-  int32_t form = 0;  // ggrs_p2p_set_unstaged: 0 default (canonical flat, or chains for few sessions),
-                     // 1 global input reads, 2 lockstep staged, 3 flat with HBM rings, 4 chains,
-                     // 5 flat with LDS rings and the queue bookkeeping, 6 canonical flat
+  ggrs::P2PForm form = ggrs::P2PForm::kDefault;  // ggrs_p2p_set_unstaged (the forms: kP2PForms, p2p_plan.h)
   bool dbg_ever = false;  // a debug flip was armed: the states may no longer be the canonical ones
   int32_t* last_saved = nullptr;  // [S], sparse saving only
   int32_t* ring_frame = nullptr;  // [R][S]: the frame each cell holds (sparse saving, scheduled mode)

@@ -39,6 +39,7 @@
 
 #include "common.h"
 #include "p2p_engine.h"
+#include "p2p_plan.h"
 
 #pragma clang fp contract(off)
 
@@ -48,7 +49,6 @@ namespace {
 
 constexpr int32_t kNull = GGRS_NULL_FRAME;
 constexpr int kQ = 128;  // INPUT_QUEUE_LENGTH (input_queue.rs:6)
-constexpr int kBlock = 64;
 
 enum : int { kCur = 0, kLconf, kDframe, kLastSaved, kDelivered, kLocalLast, kSkips, kErr, kDisc, kLastSent, kRmask, kLastCk, kPl0 };
 constexpr int kPlFields = 1;  // per player: last_frame (local_connect_status; remote players)
@@ -57,7 +57,7 @@ constexpr int kPlFields = 1;  // per player: last_frame (local_connect_status; r
 __host__ __device__ constexpr int sched_rep0(int P) { return kPl0 + kPlFields * P; }
 __host__ __device__ constexpr int sched_fields(int P) { return sched_rep0(P) + P * P; }
 constexpr uint32_t kEvPeerReport = 0x10u;  // an events byte's flag: the call carries a peer report
-__host__ __device__ constexpr int cell_dwords_s(int p) { return (state_fields(p) + 1 + 3) & ~3; }
+__host__ __device__ constexpr int cell_dwords_s(int p) { return cell_dwords(p); }
 
 struct SchedParams {
   int64_t S;
@@ -94,33 +94,7 @@ struct SchedParams {
   int32_t trace_cap;
 };
 
-// The block's LDS (dynamic): its 64 sessions' rings [R][PC][64] uint4 (+ frame tags [R][64] with
-// sparse saving; without it every frame 0 .. last save has been saved, so a cell's frame is the
-// newest one <= the last save in its slot), local queues [WL][64], and per stage of K calls the
-// calls' records [K][64] (u32, sparse saving u64) and the input rows [B + K][64] of frames / calls
-// [stage start - B, stage end) with their row tags.
-struct SchedLds {
-  uint32_t o_tags, o_lq, o_arr, o_rowtag, o_rows, total;  // byte offsets (32-bit: scalar registers are scarce)
-  uint32_t rec_b, rowtag_b, rows_b;                       // bytes of one stage buffer of each
-};
-__host__ __device__ inline uint32_t align16(uint32_t x) { return (x + 15) & ~15u; }
-__host__ __device__ inline int input_word_bytes(int P) { return P <= 1 ? 1 : (P == 2 ? 2 : 4); }
-// nbuf: stage buffers (records, row tags, rows): 2 when the control pass of stage i + 1 runs on a
-// second wave beside stage i's step loop
-__host__ __device__ inline SchedLds sched_lds(int P, int R, int sparse, int WL, int K, int B, int nbuf = 1) {
-  SchedLds l;
-  const uint32_t ring = (uint32_t)R * (cell_dwords_s(P) / 4) * kBlock * 16;
-  l.o_tags = ring;
-  l.o_lq = align16(l.o_tags + (sparse ? (uint32_t)R * kBlock * 4 : 0u));
-  l.o_arr = align16(l.o_lq + (uint32_t)WL * kBlock * input_word_bytes(P));
-  l.rec_b = align16((uint32_t)K * kBlock * (sparse ? 8 : 4));  // the calls' records
-  l.o_rowtag = l.o_arr + (uint32_t)nbuf * l.rec_b;
-  l.rowtag_b = align16((uint32_t)(K + B) * 4);
-  l.o_rows = l.o_rowtag + (uint32_t)nbuf * l.rowtag_b;
-  l.rows_b = align16((uint32_t)(K + B) * kBlock * input_word_bytes(P));
-  l.total = l.o_rows + (uint32_t)nbuf * l.rows_b;
-  return l;
-}
+// (the block's LDS: SchedLds and sched_lds, p2p_plan.h)
 constexpr int kArrTooFar = 0xfe;  // a burst of >= 254 frames: past the device queue (GGRS_E_PRECONDITION)
 
 
@@ -1059,38 +1033,8 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock) void p2p_sched_kernel
 // rollback to the player's last frame + 1 (at most one per remote player), so at most
 // max_prediction + 3 <= 15 are in flight and the chain 15 ranks later starts after this one ended;
 // and at most two start at one frame.
-constexpr int kCS = 16;          // sessions per block
-constexpr int kSL = 16;          // lanes per session: slot 0 the lineage, slots 1..15 chains
-constexpr int kChainThreads = kCS * kSL + 64;  // four step waves + the control wave
-constexpr int kMaxChainDepth = 12;              // max_prediction of the time-aligned form
-constexpr int kChainMaxK = 32;                  // calls per stage (the control wave's prefetch registers)
-
-// per (frame % TW, session): two uint4
-//   e0.x  the delivered frame of the call at this current frame that advances (the last one there)
-//   e0.y  bit 0 a call has this current frame | 1 it advances | 2-5 its disconnect mask
-//   e0.zw chain 0 starting here: delivered frame, flags (bit 0 valid | 4-7 slot | 8-11 depth |
-//         12-15 disconnect mask | 16-31 key)
-//   e1.xy chain 1 (a second chain starting at the same frame), e1.z the local players' input
-struct ChainLds {
-  uint32_t o_tab, o_rowtag, o_rows, o_arr, o_ev, o_range, o_lf, total;
-  uint32_t rowtag_b, rows_b, arr_b, ev_b;
-};
-__host__ __device__ inline ChainLds chain_lds(int P, int R, int TW, int K, int B) {
-  ChainLds l;
-  l.o_tab = (uint32_t)R * (cell_dwords_s(P) / 4) * kCS * 16;
-  l.rowtag_b = align16((uint32_t)(K + B) * 4);
-  l.rows_b = align16((uint32_t)(K + B) * kCS * input_word_bytes(P));
-  l.arr_b = align16((uint32_t)K * kCS * 4);
-  l.ev_b = align16((uint32_t)K * kCS);
-  l.o_rowtag = l.o_tab + (uint32_t)TW * kCS * 32;
-  l.o_rows = l.o_rowtag + 3 * l.rowtag_b;  // three stage buffers: the control's, the steps', the prefetch's
-  l.o_arr = l.o_rows + 3 * l.rows_b;
-  l.o_ev = l.o_arr + 2 * l.arr_b;
-  l.o_range = l.o_ev + 2 * l.ev_b;
-  l.o_lf = l.o_range + 2 * kCS * 8;
-  l.total = l.o_lf + kCS * 4 * 4;
-  return l;
-}
+// (kCS, kSL, kChainThreads, kMaxChainDepth, kChainMaxK, kChainMaxCalls and the block's LDS, ChainLds and
+// chain_lds: p2p_plan.h)
 
 // max over the 16 lanes of a DPP row, in every lane of it
 // (mov_dpp with every row and bank enabled and bound_ctrl: the DPP combiner folds each move into
@@ -1116,7 +1060,6 @@ __device__ inline uint32_t rowmax16_pk(uint32_t v) {
 #undef GGRS_PK_STEP
   return __builtin_bit_cast(uint32_t, x);
 }
-constexpr int kChainMaxCalls = 2000;  // calls per launch: chain keys (ranks) << 4 | slot fit 15 bits
 
 // A stage's global reads for the control wave (input rows and their tags, arrivals, events), held
 // in registers from their issue to their store into LDS -- one stage ahead, behind the control pass
@@ -1772,51 +1715,67 @@ int p2p_sched_enable(ggrs_p2p_engine* e) {
   return GGRS_OK;
 }
 
+}  // namespace ggrs
+
+namespace {
+
+// a kernel that takes more than 64 KB of dynamic LDS has to be told so
+template <typename K>
+hipError_t launch_sched_kernel(K kern, const SchedLaunch& L, const SchedParams& p, hipStream_t stream) {
+  if (L.lds > 64 * 1024) {
+    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
+    if (attr != hipSuccess) return attr;
+  }
+  kern<<<L.grid, L.block, L.lds, stream>>>(p);
+  return hipSuccess;
+}
+
+// The plan's selectors as template arguments.  Only the repeat-last predictor without sparse saving
+// is specialised on the local mask; sparse saving has one form per predictor (no second wave, the
+// features compiled in).
+template <int P>
+hipError_t launch_sched(const SchedLaunch& L, const SchedParams& p, hipStream_t stream) {
+  hipError_t rc = hipSuccess;
+  dispatch_bool(p.predictor != 0, [&](auto PR) {
+    constexpr int kPred = decltype(PR)::value ? 1 : 0;
+    if (p.sparse) {  // (never the time-aligned form)
+      rc = launch_sched_kernel(&p2p_sched_kernel<P, true, kPred, -1, false, true>, L, p, stream);
+      return;
+    }
+    dispatch_bool(L.feat, [&](auto FT) {
+      constexpr bool kFeat = decltype(FT)::value;
+      auto with_local = [&](auto LC) {
+        constexpr int kLocal = decltype(LC)::value;
+        if (L.chains) {
+          rc = launch_sched_kernel(&p2p_sched_chains_kernel<P, kPred, kLocal, kFeat>, L, p, stream);
+          return;
+        }
+        dispatch_bool(L.split, [&](auto SP) {
+          rc = launch_sched_kernel(&p2p_sched_kernel<P, false, kPred, kLocal, decltype(SP)::value, kFeat>, L, p, stream);
+        });
+      };
+      if constexpr (kPred == 0) dispatch_local<P>(p.local_mask, with_local);
+      else with_local(std::integral_constant<int, -1>());
+    });
+  });
+  return rc;
+}
+
+}  // namespace
+
+namespace ggrs {
+
 int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n) {
   if ((int64_t)e->current_frame + n > e->next_arrival_call)
     return set_error(GGRS_E_INVALID, "Missing arrivals: arrival rows are queued up to call %d, calls need up to %d",
                      e->next_arrival_call - 1, e->current_frame + n - 1);
-  if (n > e->cap) {  // a launch reads at most cap calls' arrival rows
-    int rc = p2p_sched_advance(e, e->cap);
-    if (rc) return rc;
-    return p2p_sched_advance(e, n - e->cap);
-  }
-  // stage geometry: B rows behind a stage's first call (a rollback's confirmed inputs reach back
-  // max_prediction frames, a burst after a stall a few more), K calls per stage as many as keep the
-  // block's LDS within its share of the CU -- at least 8
-  const int P = e->cfg.num_players;
-  int WL = 2;
-  while (WL < e->cfg.max_prediction + e->cfg.input_delay + 2) WL *= 2;
-  const int B = 2 * e->cfg.max_prediction + 4;
-  // the LDS a block may take without costing residency: 160 KB per CU shared by the blocks each CU
-  // must hold at once (65,536 sessions: four, one per SIMD -> 40 KB; 4,096 sessions: one -> all of it)
-  const int64_t blocks = grid_of(e->cfg.num_sessions, kBlock);
-  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (blocks + e->num_cus - 1) / e->num_cus));
-  const uint32_t budget = (uint32_t)(160 * 1024 / per_cu) - 1024;
-  // and at most 64 - B, so that a stage's rows fit the control pass's 64-bit change masks (its fast form)
-  // Two waves per block (the control pass of the next stage beside the step loop) when each CU holds
-  // one block: its second wave runs on a SIMD that would idle (GGRS_SCHED_SPLIT=0 turns it off)
-  const char* split_env = getenv("GGRS_SCHED_SPLIT");
-  const bool split = !e->sparse && per_cu == 1 && blocks <= e->num_cus && !(split_env && split_env[0] == '0');
-  const int nbuf = split ? 2 : 1;
-  // (the two-wave form overlaps all but the first stage's control pass, but shorter stages cost the
-  // step wave more than they hide: 4,096 sessions 180 / 170 / 158 / 156 / 156 us at 8 / 12 / 16 / 24
-  // / 42 calls per stage, profiles/r05ak_k*)
-  int K = std::max(8, std::min(64, 64 - B));
-  while (K > 8 && sched_lds(P, e->R, e->sparse, WL, K, B, nbuf).total > budget) K -= 4;
-  const size_t shm = sched_lds(P, e->R, e->sparse, WL, K, B, nbuf).total;
-  if (shm > 160 * 1024) return set_error(GGRS_E_INVALID, "max_prediction too large for the scheduled kernel's LDS");
   SchedParams p;
-  p.K = K;
-  p.B = B;
-  p.WL = WL;
   p.S = e->cfg.num_sessions;
   p.R = e->R;
   p.delay = e->cfg.input_delay;
   p.cap = e->cap;
   p.maxp = e->cfg.max_prediction;
-  p.c0 = e->current_frame;
-  p.n = n;
   p.predictor = e->cfg.predictor;
   p.sparse = e->sparse;
   p.local_mask = (uint32_t)e->cfg.local_mask;
@@ -1832,7 +1791,6 @@ int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n) {
   p.sst = e->sst;
   p.rollbacks = e->rollbacks;
   p.resim = e->resim;
-  p.TW = 0;
   p.interval = e->desync_interval;
   p.HF = e->sched_hf;
   p.rep_frame = e->rep_frame;
@@ -1842,106 +1800,43 @@ int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n) {
   p.fck = e->fck;
   p.trace = e->trace;
   p.trace_cap = e->trace ? e->cfg.trace_capacity : 0;
-  // desync detection, peer reports or the display trace: the flat kernel with their code (a session's
-  // standing reports, q.rmask, can only come from an engine given reports)
-  const bool feat = p.interval > 0 || p.reports != nullptr || p.trace_cap > 0;
-  if (int rc = e->timer.before(e->stream)) return rc;
-  hipError_t attr = hipSuccess;
-  // The time-aligned form (a session's replays on 16 lanes) for few sessions: when its blocks of 16
-  // sessions fill at most two per CU.  GGRS_SCHED_CHAINS=0 keeps the one-thread-per-session form.
-  int remote = 0;
-  for (int k = 0; k < P; k++) remote += !((e->cfg.local_mask >> k) & 1);
-  const char* chains_env = getenv("GGRS_SCHED_CHAINS");
-  const int64_t cblocks = grid_of(e->cfg.num_sessions, kCS);
-  // (lockstep mode, peer reports and the display trace take the one-thread-per-session form)
-  const bool chains = !e->sparse && e->cfg.max_prediction >= 1 && e->cfg.max_prediction <= kMaxChainDepth && remote <= 2 &&
-                      !e->peer_reports && !e->trace && !(chains_env && chains_env[0] == '0') &&
-                      (cblocks <= 2 * (int64_t)e->num_cus || (chains_env && chains_env[0] == '1'));
-  if (chains && n > kChainMaxCalls) {
-    int rc = p2p_sched_advance(e, kChainMaxCalls);
-    if (rc) return rc;
-    return p2p_sched_advance(e, n - kChainMaxCalls);
-  }
-  if (chains) {
-    // K calls per stage: the step waves trail the control wave by a stage, so shorter stages overlap
-    // more of the two; the tables hold the frames of two stages + max_prediction + the delay
-    const char* k_env = getenv("GGRS_SCHED_K");
-    int Kc = k_env ? atoi(k_env) : 16;
-    Kc = std::max(4, std::min(std::min(Kc, 64 - B), kChainMaxK));
-    int TW = 16;
-    while (TW < 2 * Kc + e->cfg.max_prediction + e->cfg.input_delay + 8) TW *= 2;
-    const ChainLds cl = chain_lds(P, e->R, TW, Kc, B);
-    if (cl.total > 160 * 1024) return set_error(GGRS_E_INVALID, "input_delay too large for the scheduled kernel's LDS");
-    p.K = Kc;
-    p.TW = TW;
-    dispatch_players(P, [&](auto PC) {
-      constexpr int PP = decltype(PC)::value;
-      auto go = [&](auto kern) {
-        if (cl.total > 64 * 1024)
-          attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)cl.total);
-        if (attr == hipSuccess) kern<<<(unsigned)cblocks, kChainThreads, cl.total, e->stream>>>(p);
-      };
-      auto go_f = [&](auto k0, auto k1) { feat ? go(k1) : go(k0); };  // (feat: desync detection here)
-      if constexpr (PP == 2) {
-        if (p.predictor == 0 && p.local_mask == 1u)
-          return go_f(&p2p_sched_chains_kernel<PP, 0, 1, false>, &p2p_sched_chains_kernel<PP, 0, 1, true>);
-        if (p.predictor == 0 && p.local_mask == 2u)
-          return go_f(&p2p_sched_chains_kernel<PP, 0, 2, false>, &p2p_sched_chains_kernel<PP, 0, 2, true>);
-      }
-      if (p.predictor == 0) go_f(&p2p_sched_chains_kernel<PP, 0, -1, false>, &p2p_sched_chains_kernel<PP, 0, -1, true>);
-      else go_f(&p2p_sched_chains_kernel<PP, 1, -1, false>, &p2p_sched_chains_kernel<PP, 1, -1, true>);
-    });
-    HIP_TRY(attr);
+  SchedPlanIn in{};
+  in.sessions = p.S;
+  in.players = e->cfg.num_players;
+  in.local_mask = p.local_mask;
+  in.input_delay = p.delay;
+  in.max_prediction = p.maxp;
+  in.R = e->R;
+  in.cap = e->cap;
+  in.predictor = p.predictor;
+  in.sparse = e->sparse != 0;
+  in.desync = p.interval > 0;
+  in.peer_reports = p.reports != nullptr;
+  in.trace = p.trace_cap > 0;
+  in.num_cus = e->num_cus;
+  in.left = n;
+  const SchedOverrides ov = sched_overrides_from_env();
+  // a long run takes several launches (p2p_plan.h); an error in a later one leaves the earlier ones run
+  while (in.left > 0) {
+    SchedLaunch L;
+    const char* msg = nullptr;
+    if (int rc = sched_plan_next(in, ov, &L, &msg)) return set_error(rc, "%s", msg);
+    p.K = L.K;
+    p.B = L.B;
+    p.WL = L.WL;
+    p.TW = L.TW;
+    p.c0 = e->current_frame;
+    p.n = L.n;
+    if (int rc = e->timer.before(e->stream)) return rc;
+    hipError_t launched = hipSuccess;
+    dispatch_players(in.players, [&](auto PC) { launched = launch_sched<decltype(PC)::value>(L, p, e->stream); });
+    HIP_TRY(launched);
     HIP_TRY(hipGetLastError());
     e->timer.count();
-    e->current_frame += n;
-    return GGRS_OK;
+    e->current_frame += L.n;
+    in.left -= L.n;
+    in.cap_left = L.cap_left;
   }
-  dispatch_players(P, [&](auto PC) {
-    constexpr int PP = decltype(PC)::value;
-    auto go = [&](auto kern) {
-      if (shm > 64 * 1024)
-        attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)shm);
-      if (attr == hipSuccess)
-        kern<<<(unsigned)grid_of(p.S, kBlock), split ? 2 * kBlock : kBlock, shm, e->stream>>>(p);
-    };
-    // (split, features) -> the kernel; sparse saving keeps the features compiled in
-    auto go4 = [&](auto k00, auto k01, auto k10, auto k11) {
-      if (split) feat ? go(k11) : go(k10);
-      else feat ? go(k01) : go(k00);
-    };
-    if (p.sparse) {
-      if (p.predictor == 0) go(&p2p_sched_kernel<PP, true, 0, -1, false, true>);
-      else go(&p2p_sched_kernel<PP, true, 1, -1, false, true>);
-    } else {
-      bool done = false;
-      if constexpr (PP == 2) {  // one local player of two, repeat-last: the usual peer, masks compile-time
-        if (p.predictor == 0 && (p.local_mask == 1u || p.local_mask == 2u)) {
-          if (p.local_mask == 1u)
-            go4(&p2p_sched_kernel<PP, false, 0, 1, false, false>, &p2p_sched_kernel<PP, false, 0, 1, false, true>,
-                &p2p_sched_kernel<PP, false, 0, 1, true, false>, &p2p_sched_kernel<PP, false, 0, 1, true, true>);
-          else
-            go4(&p2p_sched_kernel<PP, false, 0, 2, false, false>, &p2p_sched_kernel<PP, false, 0, 2, false, true>,
-                &p2p_sched_kernel<PP, false, 0, 2, true, false>, &p2p_sched_kernel<PP, false, 0, 2, true, true>);
-          done = true;
-        }
-      }
-      if (!done) {
-        if (p.predictor == 0)
-          go4(&p2p_sched_kernel<PP, false, 0, -1, false, false>, &p2p_sched_kernel<PP, false, 0, -1, false, true>,
-              &p2p_sched_kernel<PP, false, 0, -1, true, false>, &p2p_sched_kernel<PP, false, 0, -1, true, true>);
-        else
-          go4(&p2p_sched_kernel<PP, false, 1, -1, false, false>, &p2p_sched_kernel<PP, false, 1, -1, false, true>,
-              &p2p_sched_kernel<PP, false, 1, -1, true, false>, &p2p_sched_kernel<PP, false, 1, -1, true, true>);
-      }
-    }
-  });
-  HIP_TRY(attr);
-  HIP_TRY(hipGetLastError());
-  e->timer.count();
-  e->current_frame += n;
   return GGRS_OK;
 }
 
