@@ -1,5 +1,5 @@
 // common.h -- helpers shared by every HIP translation unit (engine.hip, requests.hip, branch.hip, particles.hip,
-// p2p.hip, p2p_sched.hip, codec.hip, spectator.hip; through engine.h and p2p_engine.h too).
+// p2p.hip, p2p_sched.hip, p2p_ingest.hip, codec.hip, spectator.hip; through engine.h and p2p_engine.h too).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1748,6 +1748,7 @@ int ggrs_p2p_engine_destroy(ggrs_p2p_engine_t* e) {
   (void)hipSetDevice(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   p2p_sched_free(e);
+  p2p_ingest_free(e);
   void* bufs[] = {e->cur, e->ring, e->inputs, e->queue, e->rollbacks, e->resim, e->trace, e->staging,
                   e->hist, e->cmp_mask, e->cmp_count, e->last_saved, e->ring_frame, e->ls_prog};
   for (void* b : bufs)
@@ -1874,7 +1875,13 @@ int ggrs_p2p_advance_frames(ggrs_p2p_engine_t* e, int32_t n) {
     return set_error(GGRS_E_INVALID, "Missing local input: inputs are queued up to frame %d, calls need up to %d",
                      e->next_input_frame - 1, e->current_frame + n - 1);
   HIP_TRY(hipSetDevice(e->cfg.device));
-  if (e->sched) return p2p_sched_advance(e, n);  // per-session arrival schedules (p2p_sched.hip)
+  if (e->sched) {  // per-session arrival schedules (p2p_sched.hip)
+    const int rc = p2p_sched_advance(e, n);
+    // packet feed (p2p_ingest.hip): the sessions it stopped in the calls now run get their error
+    if (e->pkt)
+      if (int rc2 = p2p_ingest_after_advance(e)) return rc ? rc : rc2;
+    return rc;
+  }
   P2PParams p;
   p.S = e->cfg.num_sessions;
   p.R = e->R;

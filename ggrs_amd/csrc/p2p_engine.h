@@ -1,6 +1,7 @@
 // p2p_engine.h -- the P2P engine object shared by p2p.hip (fixed-latency network: every kernel form,
 // desync detection, lockstep) and p2p_sched.hip (scheduled arrivals: per-session remote-arrival
-// tables, the prediction threshold and disconnects).  Host-side only; no kernels here.
+// tables, the prediction threshold and disconnects) and p2p_ingest.hip (the packet feed of the
+// scheduled mode).  Host-side only; no kernels here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,6 +64,17 @@ struct ggrs_p2p_engine {
   int32_t* rep_ll = nullptr;
   uint16_t* fck = nullptr;
   int32_t sched_hf = 0;
+  // packet feed (ggrs_p2p_set_packet_feed; p2p_ingest.hip): the remote inputs enter as the wire
+  // packets each call's poll received, and the device writes the arrival table
+  int32_t pkt = 0;                 // the mode
+  int32_t pkt_inputs = 0;          // max_packet_inputs
+  int32_t pkt_stride = 0;          // bytes per packet row
+  int32_t* pkt_last = nullptr;     // [S] the endpoint's last_recv_frame
+  int32_t* pkt_stop = nullptr;     // [S] NULL_FRAME while the feed runs; see p2p_ingest.hip
+  int32_t* pkt_status = nullptr;   // [cap][S] per call: the packet's outcome (ggrs_p2p_read_packet_results)
+  int32_t* pkt_ack = nullptr;      // [cap][S] per call: last_recv_frame after it
+  uint8_t* pkt_staging = nullptr;  // host-sourced calls: start frames, lengths, packets, events
+  size_t pkt_staging_bytes = 0;
   ggrs::SpanTimer timer;
 };
 
@@ -72,4 +84,12 @@ int p2p_sched_enable(ggrs_p2p_engine* e);
 int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n);
 int p2p_sched_free(ggrs_p2p_engine* e);
 int p2p_sched_desync_alloc(ggrs_p2p_engine* e);  // desync detection's buffers (scheduled mode)
+int32_t* p2p_sched_errors(ggrs_p2p_engine* e);    // [S] the sessions' errors (device)
+// p2p_ingest.hip (packet feed): decode n calls' packets (device pointers, [n][S] rows) into the input
+// rows and write their arrival rows; after a launch of calls, give the sessions the feed stopped in
+// those calls their error; free the feed's buffers
+int p2p_ingest_launch(ggrs_p2p_engine* e, int32_t first_call, int32_t n, const int32_t* start_frame,
+                      const int32_t* packet_len, const uint8_t* packets, const uint8_t* events);
+int p2p_ingest_after_advance(ggrs_p2p_engine* e);
+int p2p_ingest_free(ggrs_p2p_engine* e);
 }  // namespace ggrs

@@ -1688,6 +1688,8 @@ int p2p_sched_desync_alloc(ggrs_p2p_engine* e) {
   return GGRS_OK;
 }
 
+int32_t* p2p_sched_errors(ggrs_p2p_engine* e) { return e->sst + (int64_t)kErr * e->cfg.num_sessions; }
+
 int p2p_sched_enable(ggrs_p2p_engine* e) {
   const int64_t S = e->cfg.num_sessions;
   const int P = e->cfg.num_players;
@@ -1850,6 +1852,7 @@ int ggrs_p2p_set_arrival_schedule(ggrs_p2p_engine_t* e, int32_t on) {
     return set_error(GGRS_E_STATE, "the network model is part of the session's configuration (set before the first call)");
   if (!on) {
     e->sched = 0;
+    e->pkt = 0;  // (the packet feed is a form of the arrival schedules)
     return GGRS_OK;
   }
   if (e->cfg.max_prediction + e->cfg.input_delay + 2 >= kQ)
@@ -1862,6 +1865,8 @@ int ggrs_p2p_add_arrivals(ggrs_p2p_engine_t* e, int32_t first_call, int32_t n, c
                           const uint8_t* events) {
   if (!e || (!arrive_upto && n > 0)) return set_error(GGRS_E_INVALID, "null argument");
   if (!e->sched) return set_error(GGRS_E_STATE, "arrival schedules need ggrs_p2p_set_arrival_schedule(e, 1)");
+  if (e->pkt)
+    return set_error(GGRS_E_STATE, "the packet feed writes the arrival rows itself (ggrs_p2p_receive_packets)");
   if (n < 0) return set_error(GGRS_E_INVALID, "n_calls must be >= 0");
   if (first_call != e->next_arrival_call)
     return set_error(GGRS_E_INVALID, "arrivals must be added in call order (expected call %d, got %d)",

@@ -70,6 +70,9 @@ def _bind(L):
     L.ggrs_p2p_add_peer_reports.argtypes = [vp, i32, i32, vp]
     L.ggrs_p2p_read_sessions.argtypes = [vp, vp, vp, vp]
     L.ggrs_p2p_read_reports.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L.ggrs_p2p_set_packet_feed.argtypes = [vp, i32, i32]
+    L.ggrs_p2p_receive_packets.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32]
+    L.ggrs_p2p_read_packet_results.argtypes = [vp, i32, i32, vp, vp]
     for name in _lib.EXPORTS:
         if name.startswith("ggrs_p2p_"):
             getattr(L, name).restype = ctypes.c_int
@@ -284,6 +287,56 @@ class P2PEngine:
                                                   _vp(out["checksum"]), _vp(out["last_confirmed"]),
                                                   _vp(out["local_last"])))
         return out
+
+    # ---- packet feed (include/ggrs_amd.h, ggrs_p2p_*packet*; p2p_ingest.hip)
+    def set_packet_feed(self, max_packet_inputs=64, packet_stride=None):
+        """The remote inputs enter as the wire packets each call's poll received (receive_packets)
+        instead of as rows known in advance; after set_arrival_schedule, before the first call.
+        packet_stride defaults to codec.max_packet_bytes(remote players, max_packet_inputs)."""
+        remote = self.num_players - bin(self.local_mask).count("1")
+        if packet_stride is None:
+            packet_stride = int(self._L.ggrs_codec_max_packet_bytes(max(remote, 1), max_packet_inputs))
+        _lib.check(self._L.ggrs_p2p_set_packet_feed(self._h, max_packet_inputs, packet_stride))
+        self.max_packet_inputs, self.packet_stride, self.remote_players = max_packet_inputs, packet_stride, remote
+
+    def receive_packets(self, first_call, start_frame, packet_len, packets, events=None):
+        """The packets polled by calls first_call .. first_call + n - 1 (their input rows already
+        added): start_frame [n][S] int32 (negative: no packet), packet_len [n][S] int32, packets
+        [n][S][packet_stride] uint8, events [n][S] uint8 or None (add_arrivals' events) -- numpy
+        arrays, or torch tensors on the engine's device (read in place by the launch)."""
+        n, S = int(start_frame.shape[0]), self.num_sessions
+        stride = getattr(self, "packet_stride", None) or int(packets.shape[-1])
+        shapes = ((n, S), (n, S), (n, S, stride), (n, S))
+        dtypes = ("int32", "int32", "uint8", "uint8")
+        arrs = [start_frame, packet_len, packets, events]
+        dev = hasattr(packets, "data_ptr")
+        ptrs = []
+        for a, shape, dt in zip(arrs, shapes, dtypes):
+            if a is None:
+                ptrs.append(None)
+                continue
+            if dev:
+                if tuple(a.shape) != shape or not a.is_contiguous() or str(a.dtype) != "torch." + dt or not a.is_cuda:
+                    raise InvalidRequest(-1, f"device arrays must be contiguous {dt} {shape} on the device")
+                ptrs.append(ctypes.c_void_p(a.data_ptr()))
+            else:
+                a = np.ascontiguousarray(a, dt)
+                if a.shape != shape:
+                    raise InvalidRequest(-1, f"expected shape {shape}, got {a.shape}")
+                ptrs.append(a)
+        if not dev:
+            keep = ptrs
+            ptrs = [_vp(a) for a in keep]
+        _lib.check(self._L.ggrs_p2p_receive_packets(self._h, first_call, n, *ptrs, int(dev)))
+
+    def packet_results(self, first_call, n_calls):
+        """(status, ack_frame) [n][S] int32 for received calls among the last input_capacity: status 1
+        delivered new frames, 0 no packet / nothing new, a GGRS_CODEC_* code, GGRS_PACKET_NO_REFERENCE
+        or GGRS_PACKET_STOPPED; ack_frame the endpoint's last_recv_frame after the call."""
+        status = np.zeros((n_calls, self.num_sessions), np.int32)
+        ack = np.zeros((n_calls, self.num_sessions), np.int32)
+        _lib.check(self._L.ggrs_p2p_read_packet_results(self._h, first_call, n_calls, _vp(status), _vp(ack)))
+        return status, ack
 
     KERNEL_FORMS = {"default": 0, "unstaged": 1, "lockstep": 2, "flat": 3, "chains": 4, "flat_queues": 5,
                     "canonical": 6}

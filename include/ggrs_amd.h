@@ -600,6 +600,57 @@ int ggrs_p2p_read_sessions(ggrs_p2p_engine_t* eng, int32_t* frames, int32_t* ski
 int ggrs_p2p_read_reports(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, int32_t* frames,
                           uint16_t* checksums, int32_t* last_confirmed, int32_t* local_last);
 
+/* ---- Packet feed: the arrival schedules driven live.  A session's remote inputs enter as the
+ * compressed Input messages its endpoint received (UdpProtocol::on_input,
+ * src/network/protocol.rs:564-642), at the call that polled them, and the engine derives the
+ * arrival rows itself.  The live loop per call: ggrs_p2p_add_inputs (the local players' bytes of row
+ * c; the remote players' columns are ignored and hold arbitrary bytes until their packet arrives) ->
+ * ggrs_p2p_receive_packets -> ggrs_p2p_advance_frames.  One packet carries one byte per remote player
+ * per frame, ascending player order (InputBytes::to_player_inputs over the endpoint's handles); all
+ * remote players of a session share one arrival stream, as in the arrival schedules.  The host still
+ * parses the Input message envelope (start_frame; ack_frame for its own send side; connect status ->
+ * ggrs_p2p_add_peer_reports; disconnect_requested -> events).
+ * Per session last_recv_frame starts at GGRS_NULL_FRAME; a packet (start, bytes) at call c:
+ *  1. last_recv != NULL && last_recv + 1 < start is the reference's assert! (:588-590), and so is a
+ *     first packet with start != 0: the session stops at call c with GGRS_E_PRECONDITION;
+ *  2. the decode reference is the blank input while last_recv == NULL, else the remote bytes of frame
+ *     start - 1, read from input row start - 1; the reference keeps frames >= last_recv -
+ *     2 max_prediction (:636-639): an older one drops the packet (GGRS_PACKET_NO_REFERENCE), a kept
+ *     one whose row slot holds another frame by now stops the session (GGRS_E_PRECONDITION) -- so
+ *     input_capacity must cover 2 max_prediction + 1 frames behind last_recv plus the session's lag;
+ *  3. compression::decode with ggrs_codec_decode's acceptance and codes; a rejected packet is dropped
+ *     whole (more than max_packet_inputs inputs: GGRS_CODEC_E_CAP);
+ *  4. frames <= last_recv are skipped, the later ones stored into the remote columns of their rows,
+ *     last_recv = the packet's last frame; a frame whose row slot holds another frame stops the
+ *     session (GGRS_E_PRECONDITION), a last frame beyond the call index stops it with GGRS_E_INVALID
+ *     (the arrival rows' rule: remote and local inputs share a row, so a live host runs its sessions
+ *     no further ahead than its peers);
+ *  5. the call's arrival row is last_recv.
+ * A stopped session receives nothing more.  Kernel: p2p_ingest.hip. */
+#define GGRS_PACKET_NO_REFERENCE (-16) /* dropped: the decode reference (frame start - 1) is no longer kept */
+#define GGRS_PACKET_STOPPED (-17)      /* this packet stopped the session (ggrs_p2p_read_sessions has the error) */
+/* Part of the configuration (after ggrs_p2p_set_arrival_schedule(eng, 1), before the first call and
+ * the first arrivals): max_packet_inputs in 1..128 (PENDING_OUTPUT_SIZE, protocol.rs:22),
+ * packet_stride a multiple of 4, >= ggrs_codec_max_packet_bytes(remote players, max_packet_inputs)
+ * and <= 1012.  From then on ggrs_p2p_add_arrivals returns GGRS_E_STATE. */
+int ggrs_p2p_set_packet_feed(ggrs_p2p_engine_t* eng, int32_t max_packet_inputs, int32_t packet_stride);
+/* The packets polled by calls first_call .. first_call + n_calls - 1 (in call order, as
+ * ggrs_p2p_add_arrivals; their input rows already added): start_frame [n_calls][num_sessions] i32
+ * (negative: no packet), packet_len [n][S] i32, packets [n][S][packet_stride] u8, events [n][S] u8 as
+ * ggrs_p2p_add_arrivals' (NULL: none); at most one packet per session and call, the newest of the
+ * poll (a sender repeats everything unacknowledged).  on_device: the four pointers are device
+ * memory (packets dword aligned), read by a launch on the engine's stream; else host memory.
+ * GGRS_E_STATE without ggrs_p2p_set_packet_feed. */
+int ggrs_p2p_receive_packets(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls,
+                             const int32_t* start_frame, const int32_t* packet_len, const uint8_t* packets,
+                             const uint8_t* events, int32_t on_device);
+/* For received calls among the last input_capacity, [n_calls][num_sessions] each (either may be
+ * NULL): status 1 = decoded and delivered at least one new frame, 0 = no packet or nothing new, a
+ * GGRS_CODEC_E_* / GGRS_CODEC_UNSUPPORTED code = dropped as undecodable, GGRS_PACKET_NO_REFERENCE,
+ * GGRS_PACKET_STOPPED; ack_frame = last_recv_frame after the call (what send_input_ack carries). */
+int ggrs_p2p_read_packet_results(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, int32_t* status,
+                                 int32_t* ack_frame);
+
 /* ---------------------------------------------------------------------------------------------
  * Spectators: num_sessions independent SpectatorSessions (src/sessions/p2p_spectator_session.rs),
  * each following one host's confirmed input stream over its own network, each call =

@@ -28,6 +28,7 @@ const UNITS: &[(&str, &[&str])] = &[
     ("codec.hip", NONE),
     ("lane_encode.cpp", NONE),
     ("spectator.hip", ILP),
+    ("p2p_ingest.hip", NONE),
 ];
 
 fn main() {

@@ -51,6 +51,8 @@ pub const GGRS_CODEC_E_DELTA: i32 = -3;
 pub const GGRS_CODEC_E_CAP: i32 = -4;
 pub const GGRS_CODEC_E_INVALID: i32 = -5;
 pub const GGRS_CODEC_UNSUPPORTED: i32 = -6;
+pub const GGRS_PACKET_NO_REFERENCE: i32 = -16;
+pub const GGRS_PACKET_STOPPED: i32 = -17;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -322,6 +324,25 @@ extern "C" {
         checksums: *mut u16,
         last_confirmed: *mut i32,
         local_last: *mut i32,
+    ) -> i32;
+    // packet feed (p2p_ingest.hip): the remote inputs as the wire packets each call received
+    pub fn ggrs_p2p_set_packet_feed(eng: *mut ggrs_p2p_engine_t, max_packet_inputs: i32, packet_stride: i32) -> i32;
+    pub fn ggrs_p2p_receive_packets(
+        eng: *mut ggrs_p2p_engine_t,
+        first_call: i32,
+        n_calls: i32,
+        start_frame: *const i32,
+        packet_len: *const i32,
+        packets: *const u8,
+        events: *const u8,
+        on_device: i32,
+    ) -> i32;
+    pub fn ggrs_p2p_read_packet_results(
+        eng: *mut ggrs_p2p_engine_t,
+        first_call: i32,
+        n_calls: i32,
+        status: *mut i32,
+        ack_frame: *mut i32,
     ) -> i32;
 
     // ---- spectators (src/sessions/p2p_spectator_session.rs), batched
