@@ -1,7 +1,7 @@
 // p2p_engine.h -- the P2P engine object shared by p2p.hip (fixed-latency network: every kernel form,
 // desync detection, lockstep) and p2p_sched.hip (scheduled arrivals: per-session remote-arrival
 // tables, the prediction threshold and disconnects) and p2p_ingest.hip (the packet feed of the
-// scheduled mode).  Host-side only; no kernels here.
+// scheduled mode) and p2p_emit.hip (its send side).  Host-side only; no kernels here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -75,10 +75,38 @@ struct ggrs_p2p_engine {
   int32_t* pkt_ack = nullptr;      // [cap][S] per call: last_recv_frame after it
   uint8_t* pkt_staging = nullptr;  // host-sourced calls: start frames, lengths, packets, events
   size_t pkt_staging_bytes = 0;
+  // packet emit (ggrs_p2p_set_packet_emit; p2p_emit.hip): the sessions' outgoing Input messages
+  int32_t emit = 0;                 // the mode
+  int32_t emit_max = 0;             // max_pending_inputs
+  int32_t emit_stride = 0;          // bytes per emitted packet row
+  int32_t emit_next = 0;            // the next call to emit
+  int32_t* emit_ll = nullptr;       // [cap][S] per call: the local players' last queued frame after it, or
+                                    // kEmitStopped from the call that stopped the session (the scheduled kernels write it)
+  uint32_t* emit_ring = nullptr;    // [kEmitPending][S] pending_output, slot frame % kEmitPending
+  int32_t* emit_st = nullptr;       // [kEmitFields][S] the endpoint's send-side words (EmitField)
+  uint8_t* emit_staging = nullptr;  // host-sourced calls: acks, resend flags and the outputs
+  size_t emit_staging_bytes = 0;
   ggrs::SpanTimer timer;
 };
 
 namespace ggrs {
+// packet emit: PENDING_OUTPUT_SIZE (protocol.rs:22); the mark of a stopped session in emit_ll; the
+// per-session words kept between launches
+constexpr int kEmitPending = 128;
+constexpr int32_t kEmitStopped = INT32_MIN;
+enum EmitField : int {
+  kEmitLaFrame = 0,  // last_acked_input: its frame
+  kEmitLaBytes,      // ... and bytes
+  kEmitHead,         // the first pending frame (while any is pending)
+  kEmitCount,        // pending inputs
+  kEmitStatus,       // 0 open, GGRS_EMIT_CLOSED, GGRS_EMIT_DISCONNECTED
+  kEmitClosedCall,   // the call that closed the stream (-1)
+  kEmitLlPrev,       // the local players' last queued frame after the last emitted call
+  kEmitRecv,         // the endpoint's last_recv_frame after it
+  kEmitFields
+};
+// p2p_emit.hip: free the emit buffers
+int p2p_emit_free(ggrs_p2p_engine* e);
 // p2p_sched.hip: enable scheduled mode (allocate and initialise its buffers), run n calls, upload arrival rows
 int p2p_sched_enable(ggrs_p2p_engine* e);
 int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n);

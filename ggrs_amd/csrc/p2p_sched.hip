@@ -92,6 +92,11 @@ struct SchedParams {
   // it (ex_game.rs:115-127), the previous call's when it advanced nothing
   uint16_t* trace;
   int32_t trace_cap;
+  // packet emit (p2p_emit.hip; emit != 0): per call c (row c % cap) and session the local players'
+  // last queued frame after it -- the call queued a frame when it rose -- or kEmitStopped from the
+  // call that stopped the session
+  int32_t* emit_ll;
+  int32_t emit;
 };
 
 // (the block's LDS: SchedLds and sched_lds, p2p_plan.h)
@@ -484,6 +489,10 @@ __device__ inline void sched_store_report(const SchedParams& p, int32_t c, int64
   p.rep_lconf[i] = lconf;
   p.rep_ll[i] = ll;
 }
+// Packet emit: the call's row of emit_ll
+__device__ inline void sched_store_emit(const SchedParams& p, int32_t c, int64_t s, int32_t ll, bool stopped) {
+  p.emit_ll[(int64_t)(c % p.cap) * p.S + s] = stopped ? kEmitStopped : ll;
+}
 // ... and after the launch (every cell final): each report's checksum, the final cell checksum of its
 // frame -- a confirmed frame's cell is never saved again (a rollback starts after every confirmed
 // frame), so this is the checksum the reference read from the cell when it sent the report
@@ -795,6 +804,7 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock) void p2p_sched_kernel
               if (j < nj) {
                 lrec[(cb8 + j - cs) * kBlock + lt] = (Rec)(idle ? kStopBefore << 8 : recs[j]);
                 if (kFeat && p.interval > 0 && live) sched_store_report(p, cb8 + j, s, reps[j], lcs[j], lls1[j]);
+                if (kFeat && p.emit && live) sched_store_emit(p, cb8 + j, s, lls1[j], idle);
               }
             }
             continue;
@@ -817,6 +827,7 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock) void p2p_sched_kernel
           int32_t rep;
           const uint2 rr = sched_control_call<P, kSparse, kPred, kFeat>(q, env, mask_ok, cm, c, a_c, e_c, rep);
           if (kFeat && p.interval > 0 && live) sched_store_report(p, c, s, rep, lconf0, q.local_last);
+          if (kFeat && p.emit && live) sched_store_emit(p, c, s, q.local_last, q.err != 0);
           Rec r;
           if constexpr (kSparse) r = rr;
           else r = rr.x;
@@ -1407,6 +1418,11 @@ __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedPa
             if (kFeat && p.interval > 0 && live && !en) {  // (a stopped session: no report)
               for (int j = 0; j < nj; j++) sched_store_report(p, cb8 + j, s, kNull, q.lconf, q.local_last);
             }
+            if (kFeat && p.emit && live) {  // (a stopped session: the mark)
+#pragma unroll
+              for (int j = 0; j < 8; j++)
+                if (j < nj) sched_store_emit(p, cb8 + j, s, lls1[j], !en);
+            }
             continue;
           }
           q = q0;
@@ -1429,6 +1445,7 @@ __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedPa
             const uint32_t rec = sched_control_call<P, false, kPred, kFeat>(q, env, mask_ok, cm, c, a_c, e_c, rep).x;
             if (!live) continue;
             if (kFeat && p.interval > 0) sched_store_report(p, c, s, rep, lconf0, q.local_last);
+            if (kFeat && p.emit) sched_store_emit(p, c, s, q.local_last, q.err != 0);
             if (q.disc != disc0) {  // the disconnected players' last frames, frozen now
 #pragma unroll
               for (int k = 0; k < P; k++)
@@ -1802,6 +1819,8 @@ int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n) {
   p.fck = e->fck;
   p.trace = e->trace;
   p.trace_cap = e->trace ? e->cfg.trace_capacity : 0;
+  p.emit_ll = e->emit_ll;
+  p.emit = e->emit;
   SchedPlanIn in{};
   in.sessions = p.S;
   in.players = e->cfg.num_players;
@@ -1812,7 +1831,7 @@ int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n) {
   in.cap = e->cap;
   in.predictor = p.predictor;
   in.sparse = e->sparse != 0;
-  in.desync = p.interval > 0;
+  in.desync = p.interval > 0 || p.emit;  // (packet emit's row is stored where desync detection's is: the same kernels)
   in.peer_reports = p.reports != nullptr;
   in.trace = p.trace_cap > 0;
   in.num_cus = e->num_cus;
@@ -1853,6 +1872,7 @@ int ggrs_p2p_set_arrival_schedule(ggrs_p2p_engine_t* e, int32_t on) {
   if (!on) {
     e->sched = 0;
     e->pkt = 0;  // (the packet feed is a form of the arrival schedules)
+    e->emit = 0;  // (and so is packet emit)
     return GGRS_OK;
   }
   if (e->cfg.max_prediction + e->cfg.input_delay + 2 >= kQ)

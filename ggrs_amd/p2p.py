@@ -73,6 +73,9 @@ def _bind(L):
     L.ggrs_p2p_set_packet_feed.argtypes = [vp, i32, i32]
     L.ggrs_p2p_receive_packets.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32]
     L.ggrs_p2p_read_packet_results.argtypes = [vp, i32, i32, vp, vp]
+    L.ggrs_p2p_set_packet_emit.argtypes = [vp, i32, i32]
+    L.ggrs_p2p_emit_packets.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
+    L.ggrs_p2p_read_emit_state.argtypes = [vp, vp, vp, vp, vp]
     for name in _lib.EXPORTS:
         if name.startswith("ggrs_p2p_"):
             getattr(L, name).restype = ctypes.c_int
@@ -337,6 +340,63 @@ class P2PEngine:
         ack = np.zeros((n_calls, self.num_sessions), np.int32)
         _lib.check(self._L.ggrs_p2p_read_packet_results(self._h, first_call, n_calls, _vp(status), _vp(ack)))
         return status, ack
+
+    # ---- packet emit (include/ggrs_amd.h, ggrs_p2p_*emit*; p2p_emit.hip)
+    def set_packet_emit(self, max_pending_inputs=64, out_stride=None):
+        """The sessions' outgoing Input message bodies are built on the device (emit_packets); after
+        set_arrival_schedule, before the first call.  out_stride defaults to
+        codec.max_packet_bytes(local players, max_pending_inputs)."""
+        local = bin(self.local_mask).count("1")
+        if out_stride is None:
+            out_stride = int(self._L.ggrs_codec_max_packet_bytes(max(local, 1), max_pending_inputs))
+        _lib.check(self._L.ggrs_p2p_set_packet_emit(self._h, max_pending_inputs, out_stride))
+        self.max_pending_inputs, self.out_stride, self.local_players = max_pending_inputs, out_stride, local
+
+    def emit_packets(self, first_call, n_calls, ack_in=None, resend=None, out=None):
+        """The packets sent by calls first_call .. first_call + n_calls - 1 (already run, emitted in
+        order, each once): ack_in [n][S] int32 (the newest ack_frame each call's poll received,
+        NULL_FRAME none) and resend [n][S] uint8 (the retry timer fired) or None.  Returns
+        (start_frame [n][S] int32, -1 no packet; packet_len [n][S] int32; ack_frame [n][S] int32;
+        packets [n][S][out_stride] uint8) as numpy arrays -- or, with out = such a tuple of torch
+        tensors on the engine's device (ack_in and resend then device tensors too), fills and returns
+        them; the launch runs on the engine's stream (synchronize() before another stream reads)."""
+        n, S = int(n_calls), self.num_sessions
+        stride = getattr(self, "out_stride", None)
+        if stride is None:
+            _lib.check(self._L.ggrs_p2p_emit_packets(self._h, first_call, n, None, None, None, None, None, None, 0))
+        dev = out is not None
+        shapes = ((n, S), (n, S), (n, S), (n, S), (n, S), (n, S, stride))
+        dtypes = ("int32", "uint8", "int32", "int32", "int32", "uint8")
+        if dev:
+            arrs = [ack_in, resend] + list(out)
+            ptrs = []
+            for a, shape, dt in zip(arrs, shapes, dtypes):
+                if a is None:
+                    ptrs.append(None)
+                    continue
+                if (not hasattr(a, "data_ptr") or tuple(a.shape) != shape or not a.is_contiguous()
+                        or str(a.dtype) != "torch." + dt or not a.is_cuda):
+                    raise InvalidRequest(-1, f"device arrays must be contiguous {dt} {shape} on the device")
+                ptrs.append(ctypes.c_void_p(a.data_ptr()))
+            _lib.check(self._L.ggrs_p2p_emit_packets(self._h, first_call, n, *ptrs, 1))
+            return tuple(out)
+        ins = []
+        for a, shape, dt in zip((ack_in, resend), shapes, dtypes):
+            if a is not None:
+                a = np.ascontiguousarray(a, dt)
+                if a.shape != shape:
+                    raise InvalidRequest(-1, f"expected shape {shape}, got {a.shape}")
+            ins.append(a)
+        outs = [np.zeros(shape, dt) for shape, dt in zip(shapes[2:], dtypes[2:])]
+        _lib.check(self._L.ggrs_p2p_emit_packets(self._h, first_call, n, *(_vp(a) for a in ins + outs), 0))
+        return tuple(outs)
+
+    def emit_state(self):
+        """(last_acked, pending, status, closed_call) [S] int32 each: last_acked_input's frame, the
+        pending inputs, 0 / GGRS_EMIT_CLOSED / GGRS_EMIT_DISCONNECTED, and the closing call (-1)."""
+        out = [np.zeros(self.num_sessions, np.int32) for _ in range(4)]
+        _lib.check(self._L.ggrs_p2p_read_emit_state(self._h, *(_vp(a) for a in out)))
+        return tuple(out)
 
     KERNEL_FORMS = {"default": 0, "unstaged": 1, "lockstep": 2, "flat": 3, "chains": 4, "flat_queues": 5,
                     "canonical": 6}

@@ -651,6 +651,59 @@ int ggrs_p2p_receive_packets(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t
 int ggrs_p2p_read_packet_results(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, int32_t* status,
                                  int32_t* ack_frame);
 
+/* ---- Packet emit: the send side of the same endpoint.  Every session's outgoing Input message body
+ * is built on the device from the engine's own input rows: UdpProtocol::send_input
+ * (src/network/protocol.rs:421-448), send_pending_output (:450-487), pop_pending_output (:378-391, from
+ * on_input :566 and on_input_ack :644-646) and poll's retry (:333-337), called from
+ * P2PSession::advance_frame (p2p_session.rs:363-387) and poll_remote_clients (:430-478).  One endpoint
+ * per session holds all of its remote players; arrival-schedule mode is required, the packet feed is
+ * not; rollback and lockstep mode.  One pending input is one byte per local player of one frame,
+ * ascending player order (InputBytes::from_inputs, protocol.rs:52-80).  Per session last_acked starts
+ * as (GGRS_NULL_FRAME, zero bytes), pending empty, the stream open.  Call c, after it ran:
+ *  1. ack_in[c], the newest ack_frame the call's poll received (an Input message's or a bare
+ *     InputAck's; GGRS_NULL_FRAME: none), pops every pending input with frame <= it; last_acked
+ *     becomes the last one popped (a stale ack changes nothing; one beyond the newest pending frame
+ *     pops everything and last_acked is that newest pending input);
+ *  2. an events bit of a remote player at call c (Event::Disconnected -> disconnect_player_at_frame ->
+ *     endpoint.disconnect(), p2p_session.rs:618-655) closes the stream: GGRS_EMIT_CLOSED, nothing is
+ *     emitted from this call on.  Peer reports do not close it.  Divergence: the closing call itself
+ *     emits nothing, where the reference's poll could still send a timer retry before the event;
+ *  3. if call c's add_local_input was accepted (the local players' last queued frame rose: not at the
+ *     prediction threshold's repeat, not a lockstep call that waits), frame current_frame + input_delay
+ *     is pushed with the local columns of input row c; more than max_pending_inputs pending closes the
+ *     stream with GGRS_EMIT_DISCONNECTED -- the Event::Disconnected of :443-445, applied at once
+ *     (divergence: the reference's session handles it in its next poll); the overflowing call emits
+ *     nothing;
+ *  4. a packet goes out when a frame was pushed, or when resend[c] is set (the host's 200 ms retry
+ *     timer) and something is pending; at most one per call: start_frame = the first pending frame,
+ *     bytes = compression::encode(last_acked's bytes, the pending inputs), as ggrs_codec_encode;
+ *  5. ack_frame[c] = the endpoint's last_recv_frame after call c (the packet feed's, or the newest frame
+ *     of the arrival rows), written for every call: what the Input message or a bare InputAck carries;
+ *  6. a session that stopped (an error in ggrs_p2p_read_sessions) emits nothing from its stopping call on.
+ * The host still fills the envelope: peer_connect_status and disconnect_requested.  With emit
+ * configured the scheduled kernels store one more word per session and call.  Kernel: p2p_emit.hip. */
+#define GGRS_EMIT_CLOSED (-18)        /* the stream closed on an Event::Disconnected of a remote player */
+#define GGRS_EMIT_DISCONNECTED (-19)  /* more than max_pending_inputs unacknowledged inputs */
+/* Part of the configuration (after ggrs_p2p_set_arrival_schedule(eng, 1), before the first call; a
+ * local and a remote player): max_pending_inputs in 1..128 (PENDING_OUTPUT_SIZE, protocol.rs:22),
+ * out_stride a multiple of 4, >= ggrs_codec_max_packet_bytes(local players, max_pending_inputs) and
+ * <= 1012.  GGRS_E_STATE after the first call. */
+int ggrs_p2p_set_packet_emit(ggrs_p2p_engine_t* eng, int32_t max_pending_inputs, int32_t out_stride);
+/* Calls first_call .. first_call + n_calls - 1: already run, in order, each exactly once, still among
+ * the last input_capacity calls (GGRS_E_INVALID otherwise).  ack_in [n][S] i32 and resend [n][S] u8 may
+ * be NULL (none).  Outputs: start_frame [n][S] (-1: no packet), packet_len [n][S] (0: none), ack_frame
+ * [n][S], packets [n][S][out_stride]; bytes past packet_len are unspecified.  on_device: every
+ * pointer is device memory (packets dword aligned), written by a launch on the engine's stream; the
+ * caller orders its consumer after that launch.  The result does not depend on how the calls are
+ * split over ggrs_p2p_emit_packets.  GGRS_E_STATE without ggrs_p2p_set_packet_emit. */
+int ggrs_p2p_emit_packets(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, const int32_t* ack_in,
+                          const uint8_t* resend, int32_t* start_frame, int32_t* packet_len, int32_t* ack_frame,
+                          uint8_t* packets, int32_t on_device);
+/* Per session, [num_sessions] each (any may be NULL): last_acked's frame, the pending count, the status
+ * (0 open, GGRS_EMIT_CLOSED, GGRS_EMIT_DISCONNECTED) and the call at which the stream closed (-1). */
+int ggrs_p2p_read_emit_state(ggrs_p2p_engine_t* eng, int32_t* last_acked, int32_t* pending, int32_t* status,
+                             int32_t* closed_call);
+
 /* ---------------------------------------------------------------------------------------------
  * Spectators: num_sessions independent SpectatorSessions (src/sessions/p2p_spectator_session.rs),
  * each following one host's confirmed input stream over its own network, each call =

@@ -29,6 +29,7 @@ const UNITS: &[(&str, &[&str])] = &[
     ("lane_encode.cpp", NONE),
     ("spectator.hip", ILP),
     ("p2p_ingest.hip", NONE),
+    ("p2p_emit.hip", NONE),
 ];
 
 fn main() {

@@ -53,6 +53,8 @@ pub const GGRS_CODEC_E_INVALID: i32 = -5;
 pub const GGRS_CODEC_UNSUPPORTED: i32 = -6;
 pub const GGRS_PACKET_NO_REFERENCE: i32 = -16;
 pub const GGRS_PACKET_STOPPED: i32 = -17;
+pub const GGRS_EMIT_CLOSED: i32 = -18;
+pub const GGRS_EMIT_DISCONNECTED: i32 = -19;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -343,6 +345,27 @@ extern "C" {
         n_calls: i32,
         status: *mut i32,
         ack_frame: *mut i32,
+    ) -> i32;
+    // packet emit (p2p_emit.hip): the sessions' outgoing Input message bodies, built on the device
+    pub fn ggrs_p2p_set_packet_emit(eng: *mut ggrs_p2p_engine_t, max_pending_inputs: i32, out_stride: i32) -> i32;
+    pub fn ggrs_p2p_emit_packets(
+        eng: *mut ggrs_p2p_engine_t,
+        first_call: i32,
+        n_calls: i32,
+        ack_in: *const i32,
+        resend: *const u8,
+        start_frame: *mut i32,
+        packet_len: *mut i32,
+        ack_frame: *mut i32,
+        packets: *mut u8,
+        on_device: i32,
+    ) -> i32;
+    pub fn ggrs_p2p_read_emit_state(
+        eng: *mut ggrs_p2p_engine_t,
+        last_acked: *mut i32,
+        pending: *mut i32,
+        status: *mut i32,
+        closed_call: *mut i32,
     ) -> i32;
 
     // ---- spectators (src/sessions/p2p_spectator_session.rs), batched
