@@ -67,6 +67,7 @@ EXPORTS = (
     "ggrs_spectator_calls", "ggrs_spectator_synchronize", "ggrs_spectator_read_sessions",
     "ggrs_spectator_read_state", "ggrs_spectator_read_states", "ggrs_spectator_read_trace",
     "ggrs_spectator_timing_reset", "ggrs_spectator_timing_stop", "ggrs_spectator_timing_read",
+    "ggrs_spectator_set_packet_feed", "ggrs_spectator_receive_packets", "ggrs_spectator_read_packet_results",
     "ggrs_codec_encode", "ggrs_codec_decode", "ggrs_codec_encode_chunked", "ggrs_codec_decode_chunked", "ggrs_codec_max_packet_bytes", "ggrs_codec_set_direct",
 )
 

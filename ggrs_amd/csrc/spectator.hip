@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "common.h"
+#include "spectator_engine.h"
 
 using namespace ggrs;
 
@@ -64,7 +65,14 @@ struct SpecParams {
   int32_t cap;        // input rows held
   int32_t acap;       // arrival rows held (a multiple of 4)
   int32_t c0, n;      // calls c0 .. c0 + n - 1
-  int32_t row_lo, row_hi;  // input rows [row_lo, row_hi) are held when the launch starts
+  union {
+    struct {
+      int32_t row_lo, row_hi;  // input rows [row_lo, row_hi) are held when the launch starts
+    };
+    // the kFeed form, in their place (the table-fed kernels' arguments stay as they were): [S],
+    // session s holds the rows (feed_last[s] - cap, feed_last[s]]
+    const int32_t* feed_last;
+  };
   int32_t mfb, speed;
   int32_t trace_cap;
   uint32_t* cur;      // [F][S]
@@ -103,11 +111,29 @@ __global__ void spec_arrivals_kernel(const int32_t* src, int32_t* dst, int64_t S
   dst[((slot / 4) * S + s) * 4 + (slot & 3)] = src ? src[i] : 0;
 }
 
-template <int P, bool kTrace>
+// kFeed: the packet-fed engine (spectator_ingest.hip).  Each session follows a host on its own clock,
+// so the window of held rows is per session.  The feed delivers a session's frames consecutively, so
+// slot f % cap of session s holds frame f exactly when L - cap < f <= L, L the feed's last_recv of the
+// session when the launch starts: one [S] word instead of the lane-uniform (row_lo, row_hi), no tags.
+// A call's arrival word is the feed's last_recv at that call (<= L, so the not-yet-added stop cannot
+// happen) or kSpecFeedStop, at the call whose packet stopped the session.
+template <int P, bool kTrace, bool kFeed>
 __global__ __launch_bounds__(kSpecBlock) void spectator_kernel(SpecParams p) {
   const int64_t s = (int64_t)blockIdx.x * kSpecBlock + threadIdx.x;
   if (s >= p.S) return;
   const int64_t S = p.S;
+  int32_t feed_hi = 0;
+  if constexpr (kFeed) feed_hi = p.feed_last[s] + 1;
+  // the session holds the rows [row_lo(), row_hi()) when the launch starts (kFeed: row_lo() may be
+  // below 0, no frame is)
+  auto row_lo = [&]() -> int32_t {
+    if constexpr (kFeed) return feed_hi - p.cap;
+    else return p.row_lo;
+  };
+  auto row_hi = [&]() -> int32_t {
+    if constexpr (kFeed) return feed_hi;
+    else return p.row_hi;
+  };
   BoxState<P> st;
   load_state<P>(st, p.cur + s, S);
   int32_t* const sst = p.sst + s;
@@ -126,7 +152,7 @@ __global__ __launch_bounds__(kSpecBlock) void spectator_kernel(SpecParams p) {
   // the dword of frame g, if the launch holds it (a frame outside the window is never advanced:
   // its session stops first)
   auto row_of = [&](int32_t g) -> uint32_t {
-    return (g >= p.row_lo && g < p.row_hi) ? p.rows[(int64_t)(g % p.cap) * S + s] : 0u;
+    return (g >= row_lo() && g < row_hi()) ? p.rows[(int64_t)(g % p.cap) * S + s] : 0u;
   };
   uint32_t in_next = row_of(cur + 1);
   int32_t c = 0, todo = 0, adv_n = 0;
@@ -159,7 +185,9 @@ __global__ __launch_bounds__(kSpecBlock) void spectator_kernel(SpecParams p) {
         }
       }
       if (err != GGRS_E_INVALID && err != GGRS_E_PRECONDITION) {
-        if (r > lrecv && r >= p.row_hi) {
+        if (kFeed && r == kSpecFeedStop) {
+          err = GGRS_E_PRECONDITION;  // the feed stopped the session at this call (the reference's assert!)
+        } else if (r > lrecv && r >= row_hi()) {
           err = GGRS_E_INVALID;  // a frame the host has not produced yet
         } else {
           // protocol.rs:575-585: the endpoint's status, on every message
@@ -183,7 +211,7 @@ __global__ __launch_bounds__(kSpecBlock) void spectator_kernel(SpecParams p) {
             waited++;  // PredictionThreshold
           } else if (lrecv >= f + kSpecBuffer) {
             err = GGRS_E_TOO_FAR_BEHIND;  // stays: current_frame no longer moves, last_recv only grows
-          } else if (f < p.row_lo) {
+          } else if (f < row_lo()) {
             err = GGRS_E_PRECONDITION;  // the row left the engine's window
           } else {
             todo = (lrecv - cur > p.mfb) ? p.speed : 1;
@@ -234,25 +262,6 @@ __global__ __launch_bounds__(kSpecBlock) void spectator_kernel(SpecParams p) {
 
 }  // namespace
 
-struct ggrs_spectator_engine {
-  ggrs_spectator_config_t cfg{};
-  int F = 1, cap = 256, acap = 256;
-  hipStream_t stream = nullptr;
-  uint32_t* cur = nullptr;
-  int32_t* sst = nullptr;
-  uint32_t* rows = nullptr;
-  int4* recv = nullptr;   // [acap / 4][S]
-  int4* notes = nullptr;
-  uint8_t* adv = nullptr;
-  uint16_t* ck = nullptr;
-  uint8_t* staging = nullptr;
-  size_t staging_bytes = 0;
-  int32_t calls = 0;
-  int32_t next_input_frame = 0;
-  int32_t next_arrival_call = 0;
-  SpanTimer timer;
-};
-
 extern "C" {
 
 int ggrs_spectator_engine_destroy(ggrs_spectator_engine_t* e) {
@@ -262,6 +271,7 @@ int ggrs_spectator_engine_destroy(ggrs_spectator_engine_t* e) {
   void* bufs[] = {e->cur, e->sst, e->rows, e->recv, e->notes, e->adv, e->ck, e->staging};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  spectator_ingest_free(e);
   e->timer.destroy();
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -343,6 +353,7 @@ int ggrs_spectator_engine_config(const ggrs_spectator_engine_t* e, ggrs_spectato
 
 int ggrs_spectator_add_inputs(ggrs_spectator_engine_t* e, int32_t first_frame, int32_t n, const uint8_t* inputs) {
   if (!e || (!inputs && n > 0)) return set_error(GGRS_E_INVALID, "null argument");
+  if (e->pkt) return set_error(GGRS_E_STATE, "a packet-fed engine takes its inputs from ggrs_spectator_receive_packets");
   if (n < 0) return set_error(GGRS_E_INVALID, "n_frames must be >= 0");
   if (first_frame != e->next_input_frame)
     return set_error(GGRS_E_INVALID, "inputs must be added sequentially (expected frame %d, got %d)",
@@ -374,6 +385,7 @@ int ggrs_spectator_add_inputs(ggrs_spectator_engine_t* e, int32_t first_frame, i
 int ggrs_spectator_add_arrivals(ggrs_spectator_engine_t* e, int32_t first_call, int32_t n, const int32_t* recv_upto,
                                 const int32_t* notes) {
   if (!e || (!recv_upto && n > 0)) return set_error(GGRS_E_INVALID, "null argument");
+  if (e->pkt) return set_error(GGRS_E_STATE, "a packet-fed engine takes its arrivals from ggrs_spectator_receive_packets");
   if (n < 0) return set_error(GGRS_E_INVALID, "n_calls must be >= 0");
   if (first_call != e->next_arrival_call)
     return set_error(GGRS_E_INVALID, "arrivals must be added in call order (expected call %d, got %d)",
@@ -432,8 +444,12 @@ int ggrs_spectator_advance_frames(ggrs_spectator_engine_t* e, int32_t n) {
   p.acap = e->acap;
   p.c0 = e->calls;
   p.n = n;
-  p.row_lo = std::max(0, e->next_input_frame - e->cap);
-  p.row_hi = e->next_input_frame;
+  if (e->pkt) {
+    p.feed_last = e->pkt_last;
+  } else {
+    p.row_lo = std::max(0, e->next_input_frame - e->cap);
+    p.row_hi = e->next_input_frame;
+  }
   p.mfb = e->cfg.max_frames_behind;
   p.speed = e->cfg.catchup_speed;
   p.trace_cap = e->adv ? e->cfg.trace_capacity : 0;
@@ -448,8 +464,13 @@ int ggrs_spectator_advance_frames(ggrs_spectator_engine_t* e, int32_t n) {
   const unsigned grid = (unsigned)grid_of(p.S, kSpecBlock);
   dispatch_players(e->cfg.num_players, [&](auto PC) {
     constexpr int PP = decltype(PC)::value;
-    if (p.trace_cap > 0) spectator_kernel<PP, true><<<grid, kSpecBlock, 0, e->stream>>>(p);
-    else spectator_kernel<PP, false><<<grid, kSpecBlock, 0, e->stream>>>(p);
+    if (e->pkt) {
+      if (p.trace_cap > 0) spectator_kernel<PP, true, true><<<grid, kSpecBlock, 0, e->stream>>>(p);
+      else spectator_kernel<PP, false, true><<<grid, kSpecBlock, 0, e->stream>>>(p);
+    } else {
+      if (p.trace_cap > 0) spectator_kernel<PP, true, false><<<grid, kSpecBlock, 0, e->stream>>>(p);
+      else spectator_kernel<PP, false, false><<<grid, kSpecBlock, 0, e->stream>>>(p);
+    }
   });
   HIP_TRY(hipGetLastError());
   e->timer.count();

@@ -58,6 +58,9 @@ def _bind(L):
     L.ggrs_spectator_timing_reset.argtypes = [vp]
     L.ggrs_spectator_timing_stop.argtypes = [vp]
     L.ggrs_spectator_timing_read.argtypes = [vp, P(ctypes.c_float), P(i32)]
+    L.ggrs_spectator_set_packet_feed.argtypes = [vp, i32, i32, i32]
+    L.ggrs_spectator_receive_packets.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32]
+    L.ggrs_spectator_read_packet_results.argtypes = [vp, i32, i32, vp, vp]
     for name in _lib.EXPORTS:
         if name.startswith("ggrs_spectator_"):
             getattr(L, name).restype = ctypes.c_int
@@ -129,6 +132,55 @@ class SpectatorEngine:
             if nt.shape != a.shape:
                 raise InvalidRequest(-1, "notes must have recv_upto's shape")
         _lib.check(self._L.ggrs_spectator_add_arrivals(self._h, first_call, a.shape[0], _vp(a), _vp(nt)))
+
+    # ---- packet feed (include/ggrs_amd.h, ggrs_spectator_*packet*; spectator_ingest.hip)
+    def set_packet_feed(self, max_prediction=8, max_packet_inputs=64, packet_stride=None):
+        """The sessions' inputs and arrivals enter as the wire packets each call's poll received from
+        the host (receive_packets) instead of add_inputs / add_arrivals; each session follows its host
+        on the host's own clock.  Before the first input, arrival and call.  max_prediction is the
+        host endpoint's; packet_stride defaults to codec.max_packet_bytes(num_players,
+        max_packet_inputs)."""
+        if packet_stride is None:
+            packet_stride = int(self._L.ggrs_codec_max_packet_bytes(self.num_players, max_packet_inputs))
+        _lib.check(self._L.ggrs_spectator_set_packet_feed(self._h, max_prediction, max_packet_inputs, packet_stride))
+        self.max_prediction, self.max_packet_inputs, self.packet_stride = max_prediction, max_packet_inputs, packet_stride
+
+    def receive_packets(self, first_call, start_frame, packet_len, packets, notes=None, on_device=None):
+        """The newest packet each session's poll received by calls first_call .. first_call + n - 1:
+        start_frame [n][S] int32 (negative: no packet), packet_len [n][S] int32, packets
+        [n][S][packet_stride] uint8, notes [n][S] int32 (spectator_note(player, frame) or 0) or None --
+        numpy arrays, or with on_device=True (the default for tensors) torch tensors on the engine's
+        device, read in place by the launch."""
+        n, S = int(start_frame.shape[0]), self.num_sessions
+        stride = getattr(self, "packet_stride", None) or int(packets.shape[-1])
+        shapes = ((n, S), (n, S), (n, S, stride), (n, S))
+        dtypes = ("int32", "int32", "uint8", "int32")
+        dev = hasattr(packets, "data_ptr") if on_device is None else bool(on_device)
+        keep, ptrs = [], []
+        for a, shape, dt in zip((start_frame, packet_len, packets, notes), shapes, dtypes):
+            if a is None:
+                ptrs.append(None)
+            elif dev:
+                if (not hasattr(a, "data_ptr") or tuple(a.shape) != shape or not a.is_contiguous()
+                        or str(a.dtype) != "torch." + dt or not a.is_cuda):
+                    raise InvalidRequest(-1, f"device arrays must be contiguous {dt} {shape} tensors on the device")
+                ptrs.append(ctypes.c_void_p(a.data_ptr()))
+            else:
+                a = np.ascontiguousarray(a, dt)
+                if a.shape != shape:
+                    raise InvalidRequest(-1, f"expected shape {shape}, got {a.shape}")
+                keep.append(a)
+                ptrs.append(_vp(a))
+        _lib.check(self._L.ggrs_spectator_receive_packets(self._h, first_call, n, *ptrs, int(dev)))
+
+    def read_packet_results(self, first_call, n_calls):
+        """(status, ack_frame) [n][S] int32 for received calls among the last input_capacity: status 1
+        delivered new frames, 0 no packet / nothing new, a GGRS_CODEC_* code, GGRS_PACKET_NO_REFERENCE
+        or GGRS_PACKET_STOPPED; ack_frame the endpoint's last_recv_frame after the call (the InputAck)."""
+        status = np.zeros((n_calls, self.num_sessions), np.int32)
+        ack = np.zeros((n_calls, self.num_sessions), np.int32)
+        _lib.check(self._L.ggrs_spectator_read_packet_results(self._h, first_call, n_calls, _vp(status), _vp(ack)))
+        return status, ack
 
     def advance_frames(self, n=1):
         _lib.check(self._L.ggrs_spectator_advance_frames(self._h, n))

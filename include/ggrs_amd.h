@@ -790,6 +790,59 @@ int ggrs_spectator_timing_reset(ggrs_spectator_engine_t* eng);
 int ggrs_spectator_timing_stop(ggrs_spectator_engine_t* eng); /* as ggrs_timing_stop */
 int ggrs_spectator_timing_read(ggrs_spectator_engine_t* eng, float* total_ms, int32_t* launches);
 
+/* ---- The spectators' packet feed (kernel: spectator_ingest.hip): a session's inputs and arrivals
+ * enter as the compressed Input messages its endpoint received from the host, at the call that polled
+ * them -- UdpProtocol::on_input (src/network/protocol.rs:564-642) and Event::Input
+ * (p2p_spectator_session.rs:218-231) on the device.  Each session follows its host on the host's own
+ * clock: the window of input rows held is per session, the input_capacity frames up to the session's
+ * last received one, so the hosts of one engine may be any number of frames apart.
+ * Per session, last_recv starts at GGRS_NULL_FRAME.  A packet (start, bytes) at call c, in on_input's
+ * order:
+ *  1. last_recv != NULL && last_recv + 1 < start is the assert! of :588-590, and so is a first packet
+ *     with start != 0: the session stops at call c with GGRS_E_PRECONDITION;
+ *  2. the decode reference is the blank input while last_recv == NULL, else all players' bytes of
+ *     frame start - 1, the session's own row; recv_inputs keeps frames >= last_recv -
+ *     2 max_prediction (:636-639): an older one drops the packet (GGRS_PACKET_NO_REFERENCE);
+ *  3. compression::decode with ggrs_codec_decode's acceptance and codes; a rejected packet is dropped
+ *     whole (more than max_packet_inputs inputs: GGRS_CODEC_E_CAP; a packet_len outside
+ *     0..packet_stride: GGRS_CODEC_E_INVALID);
+ *  4. frames <= last_recv are skipped, the later ones are stored into their rows and last_recv
+ *     becomes the packet's last frame -- not bounded by the call index;
+ *  5. the call's recv_upto is last_recv; its note is merged as ggrs_spectator_add_arrivals' is,
+ *     whatever became of the packet (:575-585 precedes the decode).
+ * A stopped session receives nothing more; its spectator stops at call c (it changes no more, its
+ * calls trace 0 advances).  A SpectatorTooFarBehind session keeps receiving.  A session that must
+ * advance a frame at or below last_recv - input_capacity, last_recv the feed's when the launch
+ * starts -- receives were queued too far ahead of the launch for this input_capacity -- stops with
+ * GGRS_E_PRECONDITION, the existing rule per session.
+ *
+ * Part of the configuration: before the first input, arrival and call (GGRS_E_STATE after).
+ * max_prediction is the host endpoint's (builder.rs:320-329, default 8), >= 0; max_packet_inputs in
+ * 1..128; packet_stride a multiple of 4, >= ggrs_codec_max_packet_bytes(num_players,
+ * max_packet_inputs) and <= 1012; input_capacity > 2 * max_prediction + max_packet_inputs
+ * (GGRS_E_INVALID otherwise).  From then on ggrs_spectator_add_inputs and ggrs_spectator_add_arrivals
+ * return GGRS_E_STATE. */
+int ggrs_spectator_set_packet_feed(ggrs_spectator_engine_t* eng, int32_t max_prediction, int32_t max_packet_inputs,
+                                   int32_t packet_stride);
+/* The newest packet each session's poll received by calls first_call .. first_call + n_calls - 1, in
+ * call order as ggrs_spectator_add_arrivals, at most input_capacity calls ahead of the next call:
+ * start_frame [n_calls][num_sessions] i32 (< 0: no packet), packet_len [n_calls][num_sessions] i32,
+ * packets [n_calls][num_sessions][packet_stride] u8, one packet input = num_players bytes in player
+ * order (InputBytes::from_inputs, protocol.rs:52-80); notes [n_calls][num_sessions] i32
+ * (GGRS_SPECTATOR_NOTE or 0; NULL: none) -- the envelope's peer_connect_status, which the host still
+ * parses.  A malformed note in host memory is GGRS_E_INVALID; with on_device the five pointers are
+ * device memory (packets dword aligned) read by a launch on the engine's stream, and a malformed
+ * note counts as none.  GGRS_E_STATE without ggrs_spectator_set_packet_feed. */
+int ggrs_spectator_receive_packets(ggrs_spectator_engine_t* eng, int32_t first_call, int32_t n_calls,
+                                   const int32_t* start_frame, const int32_t* packet_len, const uint8_t* packets,
+                                   const int32_t* notes, int32_t on_device);
+/* [n_calls][num_sessions] i32 each, either may be NULL, for received calls among the last
+ * input_capacity: status as ggrs_p2p_read_packet_results' (1 = delivered something new, 0 = no
+ * packet or nothing new, a GGRS_CODEC_* code, GGRS_PACKET_NO_REFERENCE, GGRS_PACKET_STOPPED at the
+ * stopping call); ack_frame = last_recv after the call (what send_input_ack carries). */
+int ggrs_spectator_read_packet_results(ggrs_spectator_engine_t* eng, int32_t first_call, int32_t n_calls,
+                                       int32_t* status, int32_t* ack_frame);
+
 /* ---- Input wire codec, batched (src/network/compression.rs:14-182; bitfield-rle 0.2.1 runs,
  * bincode 1.3 fixint framing of EncodedInputSequence).  Replaces compression::encode / decode as
  * called per endpoint by UdpProtocol::send_pending_output (protocol.rs:450-480) and on_input

@@ -30,6 +30,7 @@ const UNITS: &[(&str, &[&str])] = &[
     ("spectator.hip", ILP),
     ("p2p_ingest.hip", NONE),
     ("p2p_emit.hip", NONE),
+    ("spectator_ingest.hip", NONE),
 ];
 
 fn main() {

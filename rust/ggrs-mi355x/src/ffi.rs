@@ -388,6 +388,14 @@ extern "C" {
     pub fn ggrs_spectator_timing_reset(eng: *mut ggrs_spectator_engine_t) -> i32;
     pub fn ggrs_spectator_timing_stop(eng: *mut ggrs_spectator_engine_t) -> i32;
     pub fn ggrs_spectator_timing_read(eng: *mut ggrs_spectator_engine_t, total_ms: *mut f32, launches: *mut i32) -> i32;
+    // the spectators' packet feed (UdpProtocol::on_input on the device, per-session input windows)
+    pub fn ggrs_spectator_set_packet_feed(eng: *mut ggrs_spectator_engine_t, max_prediction: i32,
+                                          max_packet_inputs: i32, packet_stride: i32) -> i32;
+    pub fn ggrs_spectator_receive_packets(eng: *mut ggrs_spectator_engine_t, first_call: i32, n_calls: i32,
+                                          start_frame: *const i32, packet_len: *const i32, packets: *const u8,
+                                          notes: *const i32, on_device: i32) -> i32;
+    pub fn ggrs_spectator_read_packet_results(eng: *mut ggrs_spectator_engine_t, first_call: i32, n_calls: i32,
+                                              status: *mut i32, ack_frame: *mut i32) -> i32;
 
     // ---- input wire codec, batched (src/network/compression.rs:14-182); device pointers
     pub fn ggrs_codec_encode(ref_: *const u8, pending: *const u8, count: *const i32, n_packets: i64,
