@@ -1749,6 +1749,7 @@ int ggrs_p2p_engine_destroy(ggrs_p2p_engine_t* e) {
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   p2p_sched_free(e);
   p2p_ingest_free(e);
+  p2p_spec_emit_free(e);
   p2p_emit_free(e);
   void* bufs[] = {e->cur, e->ring, e->inputs, e->queue, e->rollbacks, e->resim, e->trace, e->staging,
                   e->hist, e->cmp_mask, e->cmp_count, e->last_saved, e->ring_frame, e->ls_prog};

@@ -35,6 +35,7 @@
 
 #include "codec_device.h"
 #include "common.h"
+#include "emit_device.h"
 #include "p2p_engine.h"
 
 using namespace ggrs;
@@ -42,10 +43,6 @@ using namespace ggrs;
 namespace {
 
 constexpr int32_t kNull = GGRS_NULL_FRAME;
-constexpr int kEmitBlock = 64;             // sessions (threads) per block: one wave
-static_assert(kEmitBlock == 64, "the write-out loop splits a group row index by 6 bits");
-constexpr int kEmitGroup = 8;              // calls whose rows are built before a write-out, at most
-constexpr size_t kEmitLds = 64 * 1024;     // a block's packet rows of one call (and their lengths) must fit
 constexpr int kRing = kEmitPending;        // PENDING_OUTPUT_SIZE (protocol.rs:22)
 static_assert((kRing & (kRing - 1)) == 0, "ring slots are frame & (kRing - 1)");
 
@@ -68,57 +65,6 @@ struct EmitParams {
   int32_t* o_len;              // [n][S]
   int32_t* o_ack;              // [n][S]
   uint8_t* o_packets;          // [n][S][stride]
-};
-
-// bitfield-rle over a byte stream fed one byte at a time, into an LDS row (bounded by `room`:
-// ggrs_codec_max_packet_bytes covers every stream, the bound only keeps a wrong length in the row).
-// A literal stretch is written one byte past its start; its header is one byte for up to 63
-// bytes, else the stretch moves up a byte when it ends.
-struct RunWriter {
-  uint8_t* out;
-  int32_t room;
-  int32_t pos = 0;
-  int32_t run = 0;    // bytes in the open run
-  int32_t kind = -1;  // -1 none, 0 zeros, 1 0xFF, 2 literal
-  __device__ inline void put(int32_t at, uint8_t v) {
-    if (at < room) out[at] = v;
-  }
-  __device__ inline void varint(uint32_t v) {
-    do {
-      const uint8_t b = v & 0x7f;
-      v >>= 7;
-      put(pos++, b | (v ? 0x80 : 0));
-    } while (v);
-  }
-  __device__ inline void close() {
-    if (kind < 0) return;
-    if (kind < 2) {
-      varint(((uint32_t)run << 2) | (kind == 1 ? 2u : 0u) | 1u);
-    } else {
-      const uint32_t h = (uint32_t)run << 1;
-      if (h < 0x80u) {
-        put(pos, (uint8_t)h);
-        pos += 1 + run;
-      } else {  // (run <= 384: two header bytes)
-        for (int32_t i = run; i >= 1; --i)
-          if (pos + i < room) put(pos + 1 + i, out[pos + i]);
-        put(pos, (uint8_t)(h & 0x7f) | 0x80);
-        put(pos + 1, (uint8_t)(h >> 7));
-        pos += 2 + run;
-      }
-    }
-    kind = -1;
-    run = 0;
-  }
-  __device__ inline void byte(uint8_t x) {
-    const int32_t k = x == 0x00 ? 0 : (x == 0xFF ? 1 : 2);
-    if (k != kind) {
-      close();
-      kind = k;
-    }
-    if (k == 2) put(pos + 1 + run, x);
-    ++run;
-  }
 };
 
 template <int kB>
@@ -215,7 +161,7 @@ __global__ __launch_bounds__(kEmitBlock) void p2p_emit_kernel(EmitParams p) {
             // 4. send_pending_output (:450-487)
             if (status == 0 && cnt > 0 && (pushed || rs)) {
               uint8_t* row = smem + (size_t)(g * kEmitBlock + t) * pitch;
-              RunWriter w{row + 9, p.stride - 9};
+              RunWriter w{row + kEmitHeader, p.stride - kEmitHeader};
               uint32_t prev = la_bytes;
               for (int32_t i = 0; i < cnt; i++) {
                 const int32_t f = head + i;
@@ -227,14 +173,8 @@ __global__ __launch_bounds__(kEmitBlock) void p2p_emit_kernel(EmitParams p) {
                 for (int b = 0; b < B; b++) w.byte((uint8_t)(d >> (8 * b)));
               }
               w.close();
-              row[0] = 0;  // input_sizes: None (every input is the reference's size, compression.rs:27-35)
-#pragma unroll
-              for (int b = 0; b < 4; b++) {  // encoded_bytes' length, a u64
-                row[1 + b] = (uint8_t)((uint32_t)w.pos >> (8 * b));
-                row[5 + b] = 0;
-              }
               o_start = head;
-              o_len = min(9 + w.pos, p.stride);
+              o_len = emit_frame_row(row, w.pos, p.stride);
             }
           }
         }
@@ -251,23 +191,8 @@ __global__ __launch_bounds__(kEmitBlock) void p2p_emit_kernel(EmitParams p) {
     }
     if (need) atomicMax(&s_maxdw, need);
     __syncthreads();
-    // ---- the group's rows out, coalesced: dword q is column q & (2^sh - 1) of row q >> sh of
-    // [gn][kEmitBlock] -- the longest packet's dwords rounded up to a power of two, so that no index
-    // needs a division; a row's dwords past its own packet are not written
-    const int maxdw = s_maxdw;  // <= stride / 4
-    if (maxdw) {
-      const int sh = maxdw > 1 ? 32 - __clz(maxdw - 1) : 0;
-      const int total = (gn * kEmitBlock) << sh;
-#pragma unroll 4
-      for (int q = t; q < total; q += kEmitBlock) {
-        const int rowi = q >> sh, cc = q & ((1 << sh) - 1);
-        const int gg = rowi >> 6, r = rowi & (kEmitBlock - 1);
-        if (r < nb && cc < ((l_len[rowi] + 3) >> 2)) {
-          uint32_t* dst = reinterpret_cast<uint32_t*>(p.o_packets + ((int64_t)(k0 + gg) * S + s0 + r) * p.stride);
-          dst[cc] = reinterpret_cast<const uint32_t*>(smem + (size_t)rowi * pitch)[cc];
-        }
-      }
-    }
+    // ---- the group's rows out, coalesced (emit_device.h)
+    emit_write_group(smem, l_len, pitch, gn, nb, s_maxdw, p.o_packets, k0, S, s0, p.stride, t);
   }
   if (live) {
     fld(kEmitLaFrame) = la_frame;
@@ -306,6 +231,13 @@ int local_players(const ggrs_p2p_engine* e, uint32_t* lpos) {
 
 namespace ggrs {
 
+int p2p_emit_ll_alloc(ggrs_p2p_engine* e) {
+  const size_t rows = (size_t)e->cap * (size_t)e->cfg.num_sessions;
+  if (!e->emit_ll) HIP_TRY(hipMalloc(&e->emit_ll, sizeof(int32_t) * rows));
+  HIP_TRY(hipMemsetAsync(e->emit_ll, 0xff, sizeof(int32_t) * rows, e->stream));
+  return GGRS_OK;
+}
+
 int p2p_emit_free(ggrs_p2p_engine* e) {
   void* bufs[] = {e->emit_ll, e->emit_ring, e->emit_st, e->emit_staging};
   for (void* b : bufs)
@@ -341,13 +273,12 @@ int ggrs_p2p_set_packet_emit(ggrs_p2p_engine_t* e, int32_t max_pending_inputs, i
   if (out_stride > 1012 || (size_t)kEmitBlock * (odd_dword_pitch(out_stride) + sizeof(int32_t)) > kEmitLds)
     return set_error(GGRS_E_INVALID, "out_stride %d is too long (at most 1012)", out_stride);
   HIP_TRY(hipSetDevice(e->cfg.device));
-  const size_t S = (size_t)e->cfg.num_sessions, rows = (size_t)e->cap * S;
+  const size_t S = (size_t)e->cfg.num_sessions;
+  if (int rc = p2p_emit_ll_alloc(e)) return rc;
   if (!e->emit_st) {
-    HIP_TRY(hipMalloc(&e->emit_ll, sizeof(int32_t) * rows));
     HIP_TRY(hipMalloc(&e->emit_ring, sizeof(uint32_t) * (size_t)kEmitPending * S));
     HIP_TRY(hipMalloc(&e->emit_st, sizeof(int32_t) * (size_t)kEmitFields * S));
   }
-  HIP_TRY(hipMemsetAsync(e->emit_ll, 0xff, sizeof(int32_t) * rows, e->stream));
   HIP_TRY(hipMemsetAsync(e->emit_ring, 0, sizeof(uint32_t) * (size_t)kEmitPending * S, e->stream));
   emit_init_kernel<<<grid_of((int64_t)kEmitFields * (int64_t)S, 256), 256, 0, e->stream>>>(e->emit_st, (int64_t)S);
   HIP_TRY(hipGetLastError());

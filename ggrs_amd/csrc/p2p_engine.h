@@ -1,7 +1,8 @@
 // p2p_engine.h -- the P2P engine object shared by p2p.hip (fixed-latency network: every kernel form,
 // desync detection, lockstep) and p2p_sched.hip (scheduled arrivals: per-session remote-arrival
 // tables, the prediction threshold and disconnects) and p2p_ingest.hip (the packet feed of the
-// scheduled mode) and p2p_emit.hip (its send side).  Host-side only; no kernels here.
+// scheduled mode) and p2p_emit.hip (its send side) and p2p_spec_emit.hip (the send side towards the
+// sessions' spectators).  Host-side only; no kernels here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -86,6 +87,19 @@ struct ggrs_p2p_engine {
   int32_t* emit_st = nullptr;       // [kEmitFields][S] the endpoint's send-side words (EmitField)
   uint8_t* emit_staging = nullptr;  // host-sourced calls: acks, resend flags and the outputs
   size_t emit_staging_bytes = 0;
+  // spectator emit (ggrs_p2p_set_spectator_emit; p2p_spec_emit.hip): the sessions' confirmed inputs as
+  // Input messages to their spectators, spec_k endpoints per session; reads emit_ll as packet emit does
+  int32_t spec = 0;                 // the mode
+  int32_t spec_k = 0;               // spectator endpoints per session
+  int32_t spec_max = 0;             // max_pending_inputs
+  int32_t spec_stride = 0;          // bytes per emitted packet row
+  int32_t spec_q = 0;               // frames of the confirmed-input ring (2^k)
+  int32_t spec_next = 0;            // the next call to emit
+  uint32_t* spec_ring = nullptr;    // [spec_q][S] every player's confirmed byte of frame f, slot f & (spec_q - 1)
+  int32_t* spec_st = nullptr;       // [kSpecFields][S] the session's words (SpecField)
+  int32_t* spec_ep = nullptr;       // [kSpecEpFields][spec_k][S] the endpoints' words (SpecEpField)
+  uint8_t* spec_staging = nullptr;  // host-sourced calls: acks, resend flags and the outputs
+  size_t spec_staging_bytes = 0;
   ggrs::SpanTimer timer;
 };
 
@@ -105,8 +119,30 @@ enum EmitField : int {
   kEmitRecv,         // the endpoint's last_recv_frame after it
   kEmitFields
 };
-// p2p_emit.hip: free the emit buffers
+// spectator emit: the session's words and each endpoint's, kept between launches
+enum SpecField : int {
+  kSpecNext = 0,   // next_spectator_frame
+  kSpecLlPrev,     // the local players' last queued frame after the last emitted call
+  kSpecRecv,       // the newest remote frame delivered by it
+  kSpecDisc,       // the disconnected players' mask
+  kSpecLostCall,   // the call that found an input row lost (-1)
+  kSpecLf0,        // [4] a disconnected player's frozen last frame
+  kSpecFields = kSpecLf0 + 4
+};
+enum SpecEpField : int {
+  kSpecEpLaFrame = 0,  // last_acked_input: its frame
+  kSpecEpLaBytes,      // ... and bytes
+  kSpecEpPending,      // pending inputs after the last emitted call
+  kSpecEpStatus,       // 0 open, GGRS_EMIT_DISCONNECTED, GGRS_EMIT_ROW_LOST
+  kSpecEpClosedCall,   // the call that closed the endpoint (-1)
+  kSpecEpFields
+};
+// p2p_emit.hip: free packet emit's buffers and emit_ll (the engine's destruction: after p2p_spec_emit_free)
 int p2p_emit_free(ggrs_p2p_engine* e);
+// p2p_spec_emit.hip: free spectator emit's own buffers (emit_ll is p2p_emit_free's)
+int p2p_spec_emit_free(ggrs_p2p_engine* e);
+// emit_ll, shared by the two emits: allocated by the first configured, every row "nothing queued"
+int p2p_emit_ll_alloc(ggrs_p2p_engine* e);
 // p2p_sched.hip: enable scheduled mode (allocate and initialise its buffers), run n calls, upload arrival rows
 int p2p_sched_enable(ggrs_p2p_engine* e);
 int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n);

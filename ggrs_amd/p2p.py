@@ -76,6 +76,9 @@ def _bind(L):
     L.ggrs_p2p_set_packet_emit.argtypes = [vp, i32, i32]
     L.ggrs_p2p_emit_packets.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
     L.ggrs_p2p_read_emit_state.argtypes = [vp, vp, vp, vp, vp]
+    L.ggrs_p2p_set_spectator_emit.argtypes = [vp, i32, i32, i32]
+    L.ggrs_p2p_emit_spectator_packets.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
+    L.ggrs_p2p_read_spectator_emit_state.argtypes = [vp, vp, vp, vp, vp, vp]
     for name in _lib.EXPORTS:
         if name.startswith("ggrs_p2p_"):
             getattr(L, name).restype = ctypes.c_int
@@ -396,6 +399,68 @@ class P2PEngine:
         pending inputs, 0 / GGRS_EMIT_CLOSED / GGRS_EMIT_DISCONNECTED, and the closing call (-1)."""
         out = [np.zeros(self.num_sessions, np.int32) for _ in range(4)]
         _lib.check(self._L.ggrs_p2p_read_emit_state(self._h, *(_vp(a) for a in out)))
+        return tuple(out)
+
+    # ---- spectator emit (include/ggrs_amd.h, ggrs_p2p_*spectator*; p2p_spec_emit.hip)
+    def set_spectator_emit(self, num_spectators=1, max_pending_inputs=64, out_stride=None):
+        """The sessions' confirmed inputs go out to num_spectators (1..4) spectator endpoints per
+        session as Input message bodies built on the device (emit_spectator_packets); after
+        set_arrival_schedule, before the first call.  out_stride defaults to
+        codec.max_packet_bytes(num_players, max_pending_inputs)."""
+        if out_stride is None:
+            out_stride = int(self._L.ggrs_codec_max_packet_bytes(self.num_players, max_pending_inputs))
+        _lib.check(self._L.ggrs_p2p_set_spectator_emit(self._h, num_spectators, max_pending_inputs, out_stride))
+        self.num_spectators, self.spectator_max_pending, self.spectator_stride = (num_spectators, max_pending_inputs,
+                                                                                  out_stride)
+
+    def emit_spectator_packets(self, first_call, n_calls, ack_in=None, resend=None, out=None):
+        """The packets calls first_call .. first_call + n_calls - 1 (already run, emitted in order,
+        each once) send to the spectators: ack_in [n][K][S] int32 (the newest InputAck of spectator k,
+        NULL_FRAME none) and resend [n][K][S] uint8 (its retry timer fired) or None.  Returns
+        (start_frame [n][K][S] int32, -1 no packet; packet_len [n][K][S] int32; notes [n][S] int32,
+        the GGRS_SPECTATOR_NOTE words of SpectatorEngine.receive_packets; packets
+        [n][K][S][out_stride] uint8) as numpy arrays -- or, with out = such a tuple of torch tensors
+        on the engine's device (ack_in and resend then device tensors too), fills and returns them;
+        the launch runs on the engine's stream (synchronize() before another stream reads)."""
+        n, S = int(n_calls), self.num_sessions
+        stride, K = getattr(self, "spectator_stride", None), getattr(self, "num_spectators", 1)
+        if stride is None:
+            _lib.check(self._L.ggrs_p2p_emit_spectator_packets(self._h, first_call, n, None, None, None, None, None,
+                                                               None, 0))  # (the library's own error)
+            raise _lib.GgrsError(_lib.GGRS_E_STATE, "emit_spectator_packets needs set_spectator_emit")
+        dev = out is not None
+        shapes = ((n, K, S), (n, K, S), (n, K, S), (n, K, S), (n, S), (n, K, S, stride))
+        dtypes = ("int32", "uint8", "int32", "int32", "int32", "uint8")
+        if dev:
+            ptrs = []
+            for a, shape, dt in zip([ack_in, resend] + list(out), shapes, dtypes):
+                if a is None:
+                    ptrs.append(None)
+                    continue
+                if (not hasattr(a, "data_ptr") or tuple(a.shape) != shape or not a.is_contiguous()
+                        or str(a.dtype) != "torch." + dt or not a.is_cuda):
+                    raise InvalidRequest(-1, f"device arrays must be contiguous {dt} {shape} on the device")
+                ptrs.append(ctypes.c_void_p(a.data_ptr()))
+            _lib.check(self._L.ggrs_p2p_emit_spectator_packets(self._h, first_call, n, *ptrs, 1))
+            return tuple(out)
+        ins = []
+        for a, shape, dt in zip((ack_in, resend), shapes, dtypes):
+            if a is not None:
+                a = np.ascontiguousarray(a, dt)
+                if a.shape != shape:
+                    raise InvalidRequest(-1, f"expected shape {shape}, got {a.shape}")
+            ins.append(a)
+        outs = [np.zeros(shape, dt) for shape, dt in zip(shapes[2:], dtypes[2:])]
+        _lib.check(self._L.ggrs_p2p_emit_spectator_packets(self._h, first_call, n, *(_vp(a) for a in ins + outs), 0))
+        return tuple(outs)
+
+    def read_spectator_emit_state(self):
+        """(next_spectator_frame [S], last_acked [K][S], pending [K][S], status [K][S], closed_call
+        [K][S]) int32: per endpoint last_acked_input's frame, the pending inputs, 0 /
+        GGRS_EMIT_DISCONNECTED / GGRS_EMIT_ROW_LOST, and the closing call (-1)."""
+        S, K = self.num_sessions, getattr(self, "num_spectators", 1)
+        out = [np.zeros(S, np.int32)] + [np.zeros((K, S), np.int32) for _ in range(4)]
+        _lib.check(self._L.ggrs_p2p_read_spectator_emit_state(self._h, *(_vp(a) for a in out)))
         return tuple(out)
 
     KERNEL_FORMS = {"default": 0, "unstaged": 1, "lockstep": 2, "flat": 3, "chains": 4, "flat_queues": 5,

@@ -58,7 +58,8 @@ extern "C" {
  * 6: bulk reads for every-lane checks (ggrs_read_states, ggrs_p2p_read_states, ggrs_branch_read_cells);
  * lockstep mode under arrival schedules, peers' disconnect reports (ggrs_p2p_add_peer_reports);
  * added without a new version (nothing existing changed): the spectator engine and
- * GGRS_E_TOO_FAR_BEHIND */
+ * GGRS_E_TOO_FAR_BEHIND; the P2P packet feed and packet emit; the spectators' packet feed; the P2P
+ * engine's spectator emit (ggrs_p2p_set_spectator_emit) */
 #define GGRS_ABI_VERSION 6
 
 #define GGRS_OK 0
@@ -703,6 +704,77 @@ int ggrs_p2p_emit_packets(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_
  * (0 open, GGRS_EMIT_CLOSED, GGRS_EMIT_DISCONNECTED) and the call at which the stream closed (-1). */
 int ggrs_p2p_read_emit_state(ggrs_p2p_engine_t* eng, int32_t* last_acked, int32_t* pending, int32_t* status,
                              int32_t* closed_call);
+
+/* ---- Spectator emit: every session's confirmed inputs as the Input message bodies its host sends to
+ * its spectators, built on the device: P2PSession::send_confirmed_inputs_to_spectators
+ * (p2p_session.rs:716-745) with SyncLayer::confirmed_inputs (sync_layer.rs:296-310), and per spectator
+ * endpoint UdpProtocol::send_input (protocol.rs:421-448), send_pending_output (:450-487),
+ * pop_pending_output (:378-391) and poll's retry (:333-337).  K = num_spectators endpoints per session.
+ * Arrival-schedule mode is required; sparse saving, lockstep mode, the packet feed and packet emit
+ * combine with it; peers' disconnect reports do not (GGRS_E_STATE from whichever comes second).  One
+ * pending input is num_players bytes of one frame in ascending player order, the row
+ * ggrs_spectator_add_inputs takes.  Per session next_spectator_frame starts at 0; per endpoint
+ * last_acked = (GGRS_NULL_FRAME, zero bytes), pending empty, the stream open.  Call c, after it ran:
+ *  1. ack_in[c][k], the newest InputAck from spectator k (GGRS_NULL_FRAME: none), pops that endpoint's
+ *     pending inputs with frame <= it; last_acked becomes the last one popped (stale acks and acks
+ *     beyond the newest pending frame as in ggrs_p2p_emit_packets);
+ *  2. confirmed = the call's confirmed_frame() (:542-553): the minimum over connected players of the
+ *     local players' last queued frame before this call's add_local_input and of the remote players'
+ *     last received frame, under the connect status after the call's poll.  Every frame f in
+ *     [next_spectator_frame, confirmed] is pushed to every open endpoint -- a burst may confirm many
+ *     in one call: player k's byte is zero when disconnected[k] && last_frame[k] < f (blank_input),
+ *     else its confirmed input of frame f (a remote player's from input row f, a local player's from
+ *     the row of the call that queued frame f); next_spectator_frame = confirmed + 1;
+ *  3. more than max_pending_inputs pending on an endpoint closes it with GGRS_EMIT_DISCONNECTED (the
+ *     Event::Disconnected of :443-445), applied at once; the call emits nothing for it (divergence,
+ *     as packet emit's); the session's other endpoints go on;
+ *  4. an endpoint emits when the call pushed at least one frame, or resend[c][k] is set and something
+ *     is pending: start_frame = its first pending frame, bytes = compression::encode(last_acked's
+ *     bytes, the pending inputs), as ggrs_codec_encode.  Divergence: the reference queues one message
+ *     per pushed frame, each a superset of the one before; this is the last of them, all that a
+ *     receiver taking the newest packet of its poll needs;
+ *  5. notes[c] is the messages' peer_connect_status as ggrs_spectator_receive_packets takes it: 0 while
+ *     no player is disconnected; one disconnected player's GGRS_SPECTATOR_NOTE(player, last_frame) on
+ *     every call from its disconnect on; with m > 1 disconnected players the (c mod m)-th of them in
+ *     ascending player order (divergence: every reference message carries the whole status, here a
+ *     spectator learns of a player at most num_players - 1 delivered packets late; the merge is
+ *     sticky, so repetition is harmless);
+ *  6. a session that stopped (an error in ggrs_p2p_read_sessions) pushes and emits nothing from its
+ *     stopping call on (its notes are 0);
+ *  7. a frame to push that reads its input row (a remote player's byte that is not blank) whose row is
+ *     no longer among the input_capacity rows held closes the
+ *     session's open endpoints with GGRS_EMIT_ROW_LOST, and the session pushes nothing from that call
+ *     on: the emit was called too late for this input_capacity.  Emitting call c needs the rows from
+ *     next_spectator_frame on, so emit before more than input_capacity - (the longest arrival stall in
+ *     calls) - 1 further rows are added.
+ * The Input envelope's ack_frame and disconnect_requested stay with the host (a spectator sends no
+ * inputs).  The scheduled kernels store what they store for packet emit, one word per session and
+ * call; confirmed_frame and the connect status are restated by the emit from that word, the arrival
+ * rows and the events.  Kernel: p2p_spec_emit.hip. */
+#define GGRS_EMIT_ROW_LOST (-20)  /* an input row to push was overwritten before the emit read it */
+/* Part of the configuration (after ggrs_p2p_set_arrival_schedule(eng, 1), before the first call and
+ * before any peer report; a local player): num_spectators in 1..4, max_pending_inputs in 1..128,
+ * out_stride a multiple of 4, >= ggrs_codec_max_packet_bytes(num_players, max_pending_inputs) and
+ * <= 1012 (GGRS_E_INVALID otherwise).  GGRS_E_STATE after the first call, on a fixed-latency engine
+ * and with peer reports. */
+int ggrs_p2p_set_spectator_emit(ggrs_p2p_engine_t* eng, int32_t num_spectators, int32_t max_pending_inputs,
+                                int32_t out_stride);
+/* Calls first_call .. first_call + n_calls - 1: already run, in order, each exactly once, still among
+ * the last input_capacity calls (GGRS_E_INVALID otherwise).  With K = num_spectators and S =
+ * num_sessions: ack_in [n][K][S] i32 and resend [n][K][S] u8 may be NULL (none).  Outputs: start_frame
+ * [n][K][S] (-1: no packet), packet_len [n][K][S] (0: none), notes [n][S], packets
+ * [n][K][S][out_stride]; bytes past packet_len are unspecified.  For n = 1 the slices of one k are the
+ * arrays ggrs_spectator_receive_packets reads.  on_device as ggrs_p2p_emit_packets.  The result does not
+ * depend on how the calls are split over invocations.  GGRS_E_STATE without
+ * ggrs_p2p_set_spectator_emit. */
+int ggrs_p2p_emit_spectator_packets(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls,
+                                    const int32_t* ack_in, const uint8_t* resend, int32_t* start_frame,
+                                    int32_t* packet_len, int32_t* notes, uint8_t* packets, int32_t on_device);
+/* next_spectator_frame [S]; per endpoint [K][S] each: last_acked's frame, the pending count (frozen
+ * at max_pending_inputs + 1 by an overflow), the status (0 open, GGRS_EMIT_DISCONNECTED,
+ * GGRS_EMIT_ROW_LOST) and the call at which the endpoint closed (-1).  Any pointer may be NULL. */
+int ggrs_p2p_read_spectator_emit_state(ggrs_p2p_engine_t* eng, int32_t* next_spectator_frame, int32_t* last_acked,
+                                       int32_t* pending, int32_t* status, int32_t* closed_call);
 
 /* ---------------------------------------------------------------------------------------------
  * Spectators: num_sessions independent SpectatorSessions (src/sessions/p2p_spectator_session.rs),

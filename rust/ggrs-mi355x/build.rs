@@ -31,6 +31,7 @@ const UNITS: &[(&str, &[&str])] = &[
     ("p2p_ingest.hip", NONE),
     ("p2p_emit.hip", NONE),
     ("spectator_ingest.hip", NONE),
+    ("p2p_spec_emit.hip", NONE),
 ];
 
 fn main() {

@@ -55,6 +55,7 @@ pub const GGRS_PACKET_NO_REFERENCE: i32 = -16;
 pub const GGRS_PACKET_STOPPED: i32 = -17;
 pub const GGRS_EMIT_CLOSED: i32 = -18;
 pub const GGRS_EMIT_DISCONNECTED: i32 = -19;
+pub const GGRS_EMIT_ROW_LOST: i32 = -20;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -362,6 +363,33 @@ extern "C" {
     ) -> i32;
     pub fn ggrs_p2p_read_emit_state(
         eng: *mut ggrs_p2p_engine_t,
+        last_acked: *mut i32,
+        pending: *mut i32,
+        status: *mut i32,
+        closed_call: *mut i32,
+    ) -> i32;
+    // spectator emit (p2p_spec_emit.hip): the sessions' confirmed inputs to their spectators, built on the device
+    pub fn ggrs_p2p_set_spectator_emit(
+        eng: *mut ggrs_p2p_engine_t,
+        num_spectators: i32,
+        max_pending_inputs: i32,
+        out_stride: i32,
+    ) -> i32;
+    pub fn ggrs_p2p_emit_spectator_packets(
+        eng: *mut ggrs_p2p_engine_t,
+        first_call: i32,
+        n_calls: i32,
+        ack_in: *const i32,
+        resend: *const u8,
+        start_frame: *mut i32,
+        packet_len: *mut i32,
+        notes: *mut i32,
+        packets: *mut u8,
+        on_device: i32,
+    ) -> i32;
+    pub fn ggrs_p2p_read_spectator_emit_state(
+        eng: *mut ggrs_p2p_engine_t,
+        next_spectator_frame: *mut i32,
         last_acked: *mut i32,
         pending: *mut i32,
         status: *mut i32,
