@@ -72,6 +72,7 @@ struct IngestParams {
   const int32_t* len;        // [n][S]
   const uint8_t* packets;    // [n][S][stride]
   const uint8_t* ev_in;      // [n][S] or null
+  uint32_t ev_mask;          // (1 << num_players) - 1: the bits of ev_in that name a player
   int32_t* last;             // [S]
   int32_t* stop;             // [S]
   int32_t* status;           // [cap][S]
@@ -252,7 +253,9 @@ __global__ __launch_bounds__(kIngestBlock) void p2p_ingest_kernel(IngestParams p
     if (live) {
       const int64_t o = (int64_t)ci * S + s;
       p.arrive[o] = stop_now ? marker : last;
-      p.events[o] = p.ev_in ? p.ev_in[in_i] : (uint8_t)0;
+      // (bits at or above num_players name no player and are dropped here: bit 4 of a stored
+      // byte is the scheduled kernels' own peer-report flag)
+      p.events[o] = p.ev_in ? (uint8_t)(p.ev_in[in_i] & p.ev_mask) : (uint8_t)0;
       p.status[o] = status;
       p.ack[o] = last;
     }
@@ -319,6 +322,7 @@ int p2p_ingest_launch(ggrs_p2p_engine* e, int32_t first_call, int32_t n, const i
   p.len = packet_len;
   p.packets = packets;
   p.ev_in = events;
+  p.ev_mask = (1u << e->cfg.num_players) - 1u;
   p.last = e->pkt_last;
   p.stop = e->pkt_stop;
   p.status = e->pkt_status;

@@ -102,6 +102,27 @@ struct SchedParams {
 // (the block's LDS: SchedLds and sched_lds, p2p_plan.h)
 constexpr int kArrTooFar = 0xfe;  // a burst of >= 254 frames: past the device queue (GGRS_E_PRECONDITION)
 
+// The first remote frame a connected remote player's InputQueue has no room for: a call's poll that
+// delivers it stops the session, where the reference panics (`assert!(self.length <=
+// INPUT_QUEUE_LENGTH)`, input_queue.rs:207).  lconf is SyncLayer::last_confirmed_frame as the
+// previous calls left it.  Derivation, for a queue whose newest input is frame `up` and whose tail
+// entry holds frame T: length = up - T + 1, so frame `up` overflows when up - T >= 128.  T starts
+// at 0 and only discard_confirmed_frames moves it (input_queue.rs:83-101), called by
+// set_last_confirmed_frame (sync_layer.rs:313-340) with frame = last_confirmed_frame - 1 when
+// last_confirmed_frame > 0, in every call after the poll:
+//   * its clamp to last_requested_frame does not bind: the last request is of frame current - 1 (the
+//     call that advanced to `current`, or a replay's last frame; a rollback's reset_prediction is
+//     followed by that replay), and last_confirmed_frame <= current (sync_layer.rs:329);
+//   * its "delete all but most recent" branch (frame >= last_added_frame) is never taken: a
+//     connected remote player bounds confirmed_frame, so frame <= up - 1;
+//   * otherwise the tail moves to `frame` when that is ahead of it.
+// last_confirmed_frame never decreases, so T = max(0, lconf - 1) and the bound is up >= T + 128 --
+// in every mode: the session's current frame and max_prediction do not enter (a session at the
+// prediction threshold has lconf = current - max_prediction, where this is the older
+// current - max_prediction + 127; lockstep mode, whose lconf follows current, stops one frame
+// earlier than that, and a rollback session whose remote inputs run ahead of it stops later).
+__device__ __forceinline__ int32_t sched_queue_full(int32_t lconf) { return max(lconf, 1) + kQ - 1; }
+
 
 // A call's record, written by the control pass and read by the step loop (bits):
 //   0-6 d1: replay depth of the rollback (0: none) | 7 adv: the own frame advances | 8-9 stop |
@@ -176,7 +197,7 @@ __device__ __forceinline__ bool sched_fast_call(SchedCtl<P>& q, const SchedCtlEn
   const bool fast = en & (maxp > 0) & (a <= c) & (q.disc == 0u) & (!kFeat || q.rmask == 0u) & (e_c == 0u) & (q.dframe == kNull) &
                     (q.cur >= 1) & (q.cur >= lo) &
                     (q.delivered >= (kPred == 0 ? lo : lo - 1)) & (lbytes == 0u || q.local_last != kNull) &
-                    (up - q.delivered < kArrTooFar) & (up < q.cur - maxp + kQ - 1) & (mis == kNull || mis >= q.cur - maxp) &
+                    (up - q.delivered < kArrTooFar) & (up < sched_queue_full(q.lconf)) & (mis == kNull || mis >= q.cur - maxp) &
                     (!send || fts >= q.last_saved - maxp);
   const int32_t code = up - q.delivered;
   int32_t confirmed = INT32_MAX;  // confirmed_frame (:542-553), every player connected
@@ -274,9 +295,13 @@ __device__ __forceinline__ uint2 sched_control_call(SchedCtl<P>& q, const SchedC
     bool bad = false;
     if (code < 0) {  // a frame after its call: the remote peer cannot have sent it yet
       q.err = GGRS_E_INVALID;
-    } else if (code == kArrTooFar || up >= q.cur - maxp + kQ - 1) {
-      // the reference's InputQueue holds 128 inputs (input_queue.rs:6) and panics past them; the
-      // device keeps the same bound on how far the remote inputs may run ahead of the session
+    } else if (code == kArrTooFar || up >= (cb ? sched_queue_full(q.lconf) : INT32_MAX)) {
+      // the reference's InputQueue holds 128 inputs (input_queue.rs:6) and panics past them
+      // (sched_queue_full; a burst of kArrTooFar frames or more is past them wherever the tail is).
+      // With no remote player connected (cb == 0) nothing is added to any queue (handle_event
+      // drops the inputs of a disconnected player, p2p_session.rs:880-895): the arrival table's
+      // frames only move `delivered`.  (A select, not `cb && ...`: with the short-circuit form this
+      // hipcc emits an illegal compare of the LDS aperture base in this function and stops.)
       q.err = GGRS_E_PRECONDITION;
     } else {
       // add_input_by_frame's first_incorrect_frame: the first frame of the burst the session has
@@ -1897,6 +1922,20 @@ int ggrs_p2p_add_arrivals(ggrs_p2p_engine_t* e, int32_t first_call, int32_t n, c
     return set_error(GGRS_E_INVALID, "arrival queue full (capacity %d calls)", e->cap);
   HIP_TRY(hipSetDevice(e->cfg.device));
   const int64_t S = e->cfg.num_sessions;
+  // The events bytes as the device keeps them: bits at or above num_players name no player (the
+  // reference has none to disconnect) and are dropped here, where the bytes enter device memory --
+  // bit 4 of a stored byte is the scheduled kernels' own peer-report flag (kEvPeerReport), which
+  // only the kernels' staging may set.
+  std::vector<uint8_t> masked;
+  if (events) {
+    const uint8_t keep = (uint8_t)((1u << e->cfg.num_players) - 1u);
+    masked.assign(events, events + (size_t)n * S);
+    for (uint8_t& b : masked) b &= keep;
+  }
+  struct StreamDrain {  // no copy may still read `masked` when it is freed, on an early return either
+    hipStream_t stream;
+    ~StreamDrain() { (void)hipStreamSynchronize(stream); }
+  } drain{e->stream};
   // rows wrap at cap: copy in at most two pieces per table
   for (int32_t k = 0; k < n;) {
     const int32_t slot = (first_call + k) % e->cap;
@@ -1904,7 +1943,7 @@ int ggrs_p2p_add_arrivals(ggrs_p2p_engine_t* e, int32_t first_call, int32_t n, c
     HIP_TRY(hipMemcpyAsync(e->arrive + (int64_t)slot * S, arrive_upto + (int64_t)k * S, sizeof(int32_t) * m * S,
                            hipMemcpyHostToDevice, e->stream));
     if (events)
-      HIP_TRY(hipMemcpyAsync(e->events + (int64_t)slot * S, events + (int64_t)k * S, (size_t)m * S,
+      HIP_TRY(hipMemcpyAsync(e->events + (int64_t)slot * S, masked.data() + (int64_t)k * S, (size_t)m * S,
                              hipMemcpyHostToDevice, e->stream));
     else
       HIP_TRY(hipMemsetAsync(e->events + (int64_t)slot * S, 0, (size_t)m * S, e->stream));

@@ -560,8 +560,10 @@ int ggrs_p2p_debug_desync(ggrs_p2p_engine_t* eng, int32_t session, int32_t frame
  * checksum after the call's last AdvanceFrame, ggrs_p2p_read_trace indexed by call); peers' disconnect reports
  * (ggrs_p2p_add_peer_reports) after (2); desync detection (ggrs_p2p_set_desync_detection, without sparse
  * saving) per session: ggrs_p2p_read_reports; remote_latency is ignored.  A session whose
- * call would make the reference panic (a remote input no longer in the input rows or more than
- * 126 - max_prediction frames ahead of the session, a rollback to a frame that is not in the past
+ * call would make the reference panic (a remote input no longer in the input rows, or one that a
+ * remote InputQueue's 128 entries have no room for -- a frame at or past max(last_confirmed_frame, 1)
+ * + 127, the queue's tail standing at last_confirmed_frame - 1, input_queue.rs:83-101, :207 --,
+ * a rollback to a frame that is not in the past
  * or older than the input queues hold, no connected player) or whose arrival row names a frame after its call (GGRS_E_INVALID) stops
  * there with that error (ggrs_p2p_read_sessions); the other sessions run on.  Kernel:
  * p2p_sched.hip. */
@@ -569,7 +571,9 @@ int ggrs_p2p_debug_desync(ggrs_p2p_engine_t* eng, int32_t session, int32_t frame
 int ggrs_p2p_set_arrival_schedule(ggrs_p2p_engine_t* eng, int32_t on);
 /* arrive_upto [n_calls][num_sessions] i32: the newest remote frame delivered by each call (<= the
  * call's index; at or below what already arrived delivers nothing); events [n_calls][num_sessions]
- * u8 (NULL: none).  Calls in order from 0, at most input_capacity calls ahead of the next call. */
+ * u8 (NULL: none; bit k: Event::Disconnected of remote player k -- bits at or above num_players are
+ * ignored, as the reference has no such player).  Calls in order from 0, at most input_capacity
+ * calls ahead of the next call. */
 int ggrs_p2p_add_arrivals(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, const int32_t* arrive_upto,
                           const uint8_t* events);
 /* A peer's connect status as its input messages carry it (peer_connect_status): remote player
@@ -638,7 +642,7 @@ int ggrs_p2p_set_packet_feed(ggrs_p2p_engine_t* eng, int32_t max_packet_inputs, 
 /* The packets polled by calls first_call .. first_call + n_calls - 1 (in call order, as
  * ggrs_p2p_add_arrivals; their input rows already added): start_frame [n_calls][num_sessions] i32
  * (negative: no packet), packet_len [n][S] i32, packets [n][S][packet_stride] u8, events [n][S] u8 as
- * ggrs_p2p_add_arrivals' (NULL: none); at most one packet per session and call, the newest of the
+ * ggrs_p2p_add_arrivals' (NULL: none; bits at or above num_players ignored); at most one packet per session and call, the newest of the
  * poll (a sender repeats everything unacknowledged).  on_device: the four pointers are device
  * memory (packets dword aligned), read by a launch on the engine's stream; else host memory.
  * GGRS_E_STATE without ggrs_p2p_set_packet_feed. */

@@ -59,13 +59,9 @@ def parity_case(P, local, delay, mp, K, sparse):
     mask = sum(1 << k for k in local)
     rows = np.random.default_rng(0x5EC + P + delay).integers(0, 256, (CALLS, S, P)).astype(np.uint8)
     arrive, events = M.schedules(S, CALLS, 16, 31 + P + delay, mask, P, disconnect_every=5, second_every=10)
-    if mp == 0:
-        # lockstep: a session advances on every other call at best, so its remote players send at half
-        # the call rate.  At the call rate they run 126..128 frames ahead within the run, where the
-        # oracle's InputQueue panics and the control pass's bound (up >= current_frame + 127, the
-        # parent's) stops some sessions a call or more later: a known discrepancy of the scheduled
-        # kernels in lockstep mode ("A known discrepancy it met"), not of the emit
-        arrive = np.where(arrive < 0, arrive, arrive // 2).astype(np.int32)
+    # (lockstep, mp 0: a session advances on every other call at best while its remote players send at
+    # the call rate, so most sessions reach the InputQueue's 128 entries within the run and stop
+    # there, in the engine at the oracle's call: tests/test_gpu_p2p_queue_bound.py)
     for s in STOPPED:
         arrive[:, s] = np.maximum(np.arange(CALLS) - 1, -1)
         arrive[:270, s] = -1

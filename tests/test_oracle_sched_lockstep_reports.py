@@ -38,12 +38,17 @@ def test_lockstep_jitter_advances_exactly_when_confirmed(oracle):
     """A call advances exactly when last_confirmed_frame == current_frame: every remote input of the
     current frame delivered and the local one queued by an earlier call (the call's own local input
     is registered after the confirmed frame is taken, p2p_session.rs:314-377, so at input delay 0 a
-    session advances at most every other call); 240 calls keep the remote queue below its 128."""
-    calls, P = 240, 2
-    inp = o.gen_inputs(o.session_seed(4), calls, P, 1)
-    upto = o.stall_schedule(calls, 8, 17, stall_every=60)
+    session advances at most every other call) -- up to the call where the remote queue, which the
+    session falls behind by a frame every two calls, would pass its 128 entries (the reference
+    panics; tests/input_queue_model.py says where), which 320 calls reach."""
+    from tests import input_queue_model
+    total, P = 320, 2
+    inp = o.gen_inputs(o.session_seed(4), total, P, 1)
+    upto = o.stall_schedule(total, 8, 17, stall_every=60)
     a = o.p2p_sched_run(inp, upto, num_players=P, max_prediction=0)
-    assert a["rc"] == 0 and a["result"].rollbacks == 0 and a["result"].n_save == 0
+    calls = a["result"].frames_done
+    assert a["rc"] == -4 and calls > 240 and a["result"].rollbacks == 0 and a["result"].n_save == 0
+    assert input_queue_model.first_overflow_call(upto, a["advanced"][:calls], True, 0, 0) == calls
     cur, ll, dl = 0, -1, -1
     for c in range(calls):
         dl = max(dl, int(upto[c]))
