@@ -1,7 +1,9 @@
 // codec_device.h -- device routines of GGRS's input wire codec (src/network/compression.rs) shared
-// by the batch codec (codec.hip) and the P2P packet feed (p2p_ingest.hip): the LEB128 reader, the
-// packet validation (every check of compression::decode, in the reference's order) and the run
-// expansion of an already validated packet.  Wire format: see codec.hip.
+// by the batch codec (codec.hip), the two packet feeds (through ingest_device.h: p2p_ingest.hip and
+// spectator_ingest.hip) and the two send sides (through emit_device.h: p2p_emit.hip and
+// p2p_spec_emit.hip): the LEB128 reader, the packet validation (every check of compression::decode,
+// in the reference's order), the run expansion of an already validated packet and the LDS row pitch.
+// Wire format: see codec.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,7 +31,7 @@ __device__ inline bool get_varint(const uint8_t* in, int64_t n, int64_t& pos, ui
 
 // LDS rows are padded to an odd number of dwords so that threads stepping through their own rows in
 // lockstep spread over the banks.
-__host__ __device__ inline int odd_dword_pitch(int bytes) {
+__host__ __device__ constexpr int odd_dword_pitch(int bytes) {
   int dw = (bytes + 3) / 4;
   if ((dw & 1) == 0) dw += 1;
   return dw * 4;

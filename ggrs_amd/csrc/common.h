@@ -85,6 +85,110 @@ struct SpanTimer {
   }
 };
 
+// A device staging buffer that only grows: at least `bytes` long afterwards.
+inline int grow_staging(uint8_t** buf, size_t* have, size_t bytes) {
+  if (bytes <= *have) return GGRS_OK;
+  if (*buf) HIP_TRY(hipFree(*buf));  // (waits for the launches that read it)
+  *buf = nullptr;
+  *have = 0;
+  HIP_TRY(hipMalloc(buf, bytes));
+  *have = bytes;
+  return GGRS_OK;
+}
+
+// The host side of a packet feed (ggrs_p2p_set_packet_feed, ggrs_spectator_set_packet_feed): the
+// buffers the ingest kernels keep between launches (ingest_device.h's IngestFeed) and the feed's
+// configuration, embedded in both engines.
+struct PacketFeedState {
+  int32_t* last = nullptr;     // [S] the endpoint's last_recv_frame
+  int32_t* stop = nullptr;     // [S] NULL_FRAME while the feed runs, else the feed's own word for the stopping call
+  int32_t* status = nullptr;   // [cap][S] per call: the packet's outcome (ggrs_*_read_packet_results)
+  int32_t* ack = nullptr;      // [cap][S] per call: last_recv_frame after it
+  uint8_t* staging = nullptr;  // host-sourced calls on their way to the kernel
+  size_t staging_bytes = 0;
+  int32_t inputs = 0;          // max_packet_inputs
+  int32_t stride = 0;          // bytes per packet row
+
+  // max_packet_inputs and packet_stride for packet inputs of `bytes` bytes; max_stride: the longest
+  // row the ingest kernels stage
+  static int check(int bytes, int32_t max_packet_inputs, int32_t packet_stride, int32_t max_stride) {
+    if (max_packet_inputs < 1 || max_packet_inputs > 128)
+      return set_error(GGRS_E_INVALID, "max_packet_inputs must be in 1..128 (PENDING_OUTPUT_SIZE), got %d", max_packet_inputs);
+    const int32_t need = ggrs_codec_max_packet_bytes(bytes, max_packet_inputs);
+    if (packet_stride < need || packet_stride % 4)
+      return set_error(GGRS_E_INVALID, "packet_stride must be a multiple of 4 and >= ggrs_codec_max_packet_bytes(%d, %d) = %d, got %d",
+                       bytes, max_packet_inputs, need, packet_stride);
+    if (packet_stride > max_stride)
+      return set_error(GGRS_E_INVALID, "packet_stride %d is too long (at most %d)", packet_stride, max_stride);
+    return GGRS_OK;
+  }
+  // (re)configure: the buffers of S sessions and cap calls, every session before its first packet
+  int reset(size_t S, size_t cap, int32_t max_packet_inputs, int32_t packet_stride, hipStream_t stream) {
+    const size_t rows = cap * S;
+    if (!last) {
+      HIP_TRY(hipMalloc(&last, sizeof(int32_t) * S));
+      HIP_TRY(hipMalloc(&stop, sizeof(int32_t) * S));
+      HIP_TRY(hipMalloc(&status, sizeof(int32_t) * rows));
+      HIP_TRY(hipMalloc(&ack, sizeof(int32_t) * rows));
+    }
+    HIP_TRY(hipMemsetAsync(last, 0xff, sizeof(int32_t) * S, stream));  // NULL_FRAME
+    HIP_TRY(hipMemsetAsync(stop, 0xff, sizeof(int32_t) * S, stream));
+    HIP_TRY(hipMemsetAsync(status, 0, sizeof(int32_t) * rows, stream));
+    HIP_TRY(hipMemsetAsync(ack, 0xff, sizeof(int32_t) * rows, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    inputs = max_packet_inputs;
+    stride = packet_stride;
+    return GGRS_OK;
+  }
+  void release() {
+    void* bufs[] = {last, stop, status, ack, staging};
+    for (void* b : bufs)
+      if (b) (void)hipFree(b);
+    last = stop = status = ack = nullptr;
+    staging = nullptr;
+    staging_bytes = 0;
+  }
+  // Host rows of `rows` (call, session) pairs into the staging buffer, [start][len][packets][extra]:
+  // the pointers become the device copies.  *extra: the feed's own per-row array (1 or 4 bytes a row), or null.
+  template <typename T>
+  int stage(size_t rows, const int32_t** start, const int32_t** len, const uint8_t** packets, const T** extra,
+            hipStream_t stream) {
+    const size_t pk_bytes = rows * (size_t)stride, extra_bytes = sizeof(T);
+    if (int rc = grow_staging(&staging, &staging_bytes, rows * 8 + pk_bytes + rows * extra_bytes)) return rc;
+    uint8_t* d_start = staging;
+    uint8_t* d_len = d_start + 4 * rows;
+    uint8_t* d_pk = d_len + 4 * rows;
+    T* d_extra = reinterpret_cast<T*>(d_pk + pk_bytes);  // (stride is a multiple of 4: aligned)
+    // (stream order keeps an earlier launch's reads of the staging buffer ahead of these copies)
+    HIP_TRY(hipMemcpyAsync(d_start, *start, 4 * rows, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_len, *len, 4 * rows, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_pk, *packets, pk_bytes, hipMemcpyHostToDevice, stream));
+    if (*extra) HIP_TRY(hipMemcpyAsync(d_extra, *extra, rows * extra_bytes, hipMemcpyHostToDevice, stream));
+    *start = reinterpret_cast<const int32_t*>(d_start);
+    *len = reinterpret_cast<const int32_t*>(d_len);
+    *packets = d_pk;
+    if (*extra) *extra = d_extra;
+    return GGRS_OK;
+  }
+  // status and ack of calls first_call .. first_call + n - 1 (either may be null) of `received` calls
+  int read(int32_t first_call, int32_t n, int32_t received, int32_t cap, int64_t S, int32_t* o_status, int32_t* o_ack,
+           hipStream_t stream) const {
+    if (n < 0 || first_call < 0 || (int64_t)first_call + n > received || first_call < received - cap)
+      return set_error(GGRS_E_INVALID, "calls %d .. %d are not among the last %d calls received (%d received)",
+                       first_call, first_call + n - 1, cap, received);
+    for (int32_t k = 0; k < n;) {  // rows wrap at cap: at most two pieces
+      const int32_t slot = (first_call + k) % cap;
+      const int32_t m = n - k < cap - slot ? n - k : cap - slot;
+      const size_t off = (size_t)slot * S, dst = (size_t)k * S, cnt = (size_t)m * S;
+      if (o_status) HIP_TRY(hipMemcpyAsync(o_status + dst, status + off, 4 * cnt, hipMemcpyDeviceToHost, stream));
+      if (o_ack) HIP_TRY(hipMemcpyAsync(o_ack + dst, ack + off, 4 * cnt, hipMemcpyDeviceToHost, stream));
+      k += m;
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return GGRS_OK;
+  }
+};
+
 // Cache-policy operand of the raw buffer store builtins on gfx950: sc1, a write-through store.
 // Used for saves a launch does not read back from L2 soon, so they drain to memory while the
 // kernel runs rather than in the end-of-kernel write-back of every dirtied L2 line.

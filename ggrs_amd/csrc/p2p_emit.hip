@@ -312,13 +312,7 @@ int ggrs_p2p_emit_packets(ggrs_p2p_engine_t* e, int32_t first_call, int32_t n, c
   uint8_t *d_ack_in = nullptr, *d_resend = nullptr, *d_start = nullptr, *d_len = nullptr, *d_ack = nullptr, *d_pk = nullptr;
   if (!on_device) {  // through the staging buffer: [ack_in][start][len][ack][packets][resend]
     const size_t bytes = rows * (16 + stride + 1);
-    if (bytes > e->emit_staging_bytes) {
-      if (e->emit_staging) HIP_TRY(hipFree(e->emit_staging));
-      e->emit_staging = nullptr;
-      e->emit_staging_bytes = 0;
-      HIP_TRY(hipMalloc(&e->emit_staging, bytes));
-      e->emit_staging_bytes = bytes;
-    }
+    if (int rc = grow_staging(&e->emit_staging, &e->emit_staging_bytes, bytes)) return rc;
     d_ack_in = e->emit_staging;
     d_start = d_ack_in + 4 * rows;
     d_len = d_start + 4 * rows;
@@ -342,7 +336,7 @@ int ggrs_p2p_emit_packets(ggrs_p2p_engine_t* e, int32_t first_call, int32_t n, c
   p.inputs = e->inputs;
   p.ll = e->emit_ll;
   p.arrive = e->arrive;
-  p.pkt_ack = e->pkt_ack;
+  p.pkt_ack = e->feed.ack;
   p.events = e->events;
   p.ring = e->emit_ring;
   p.st = e->emit_st;

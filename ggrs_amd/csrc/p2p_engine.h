@@ -68,14 +68,7 @@ struct ggrs_p2p_engine {
   // packet feed (ggrs_p2p_set_packet_feed; p2p_ingest.hip): the remote inputs enter as the wire
   // packets each call's poll received, and the device writes the arrival table
   int32_t pkt = 0;                 // the mode
-  int32_t pkt_inputs = 0;          // max_packet_inputs
-  int32_t pkt_stride = 0;          // bytes per packet row
-  int32_t* pkt_last = nullptr;     // [S] the endpoint's last_recv_frame
-  int32_t* pkt_stop = nullptr;     // [S] NULL_FRAME while the feed runs; see p2p_ingest.hip
-  int32_t* pkt_status = nullptr;   // [cap][S] per call: the packet's outcome (ggrs_p2p_read_packet_results)
-  int32_t* pkt_ack = nullptr;      // [cap][S] per call: last_recv_frame after it
-  uint8_t* pkt_staging = nullptr;  // host-sourced calls: start frames, lengths, packets, events
-  size_t pkt_staging_bytes = 0;
+  ggrs::PacketFeedState feed;      // (stop: see p2p_ingest.hip; staged beside the packets: the calls' events)
   // packet emit (ggrs_p2p_set_packet_emit; p2p_emit.hip): the sessions' outgoing Input messages
   int32_t emit = 0;                 // the mode
   int32_t emit_max = 0;             // max_pending_inputs

@@ -480,13 +480,7 @@ int ggrs_p2p_emit_spectator_packets(ggrs_p2p_engine_t* e, int32_t first_call, in
   uint8_t *d_ack_in = nullptr, *d_resend = nullptr, *d_start = nullptr, *d_len = nullptr, *d_notes = nullptr, *d_pk = nullptr;
   if (!on_device) {  // through the staging buffer: [ack_in][start][len][notes][packets][resend]
     const size_t bytes = rows * (12 + stride + 1) + 4 * nS;
-    if (bytes > e->spec_staging_bytes) {
-      if (e->spec_staging) HIP_TRY(hipFree(e->spec_staging));
-      e->spec_staging = nullptr;
-      e->spec_staging_bytes = 0;
-      HIP_TRY(hipMalloc(&e->spec_staging, bytes));
-      e->spec_staging_bytes = bytes;
-    }
+    if (int rc = grow_staging(&e->spec_staging, &e->spec_staging_bytes, bytes)) return rc;
     d_ack_in = e->spec_staging;
     d_start = d_ack_in + 4 * rows;
     d_len = d_start + 4 * rows;
@@ -513,7 +507,7 @@ int ggrs_p2p_emit_spectator_packets(ggrs_p2p_engine_t* e, int32_t first_call, in
   p.row_tag = e->row_tag;
   p.ll = e->emit_ll;
   p.arrive = e->arrive;
-  p.pkt_ack = e->pkt_ack;
+  p.pkt_ack = e->feed.ack;
   p.events = e->events;
   p.ring = e->spec_ring;
   p.st = e->spec_st;

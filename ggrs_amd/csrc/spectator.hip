@@ -445,7 +445,7 @@ int ggrs_spectator_advance_frames(ggrs_spectator_engine_t* e, int32_t n) {
   p.c0 = e->calls;
   p.n = n;
   if (e->pkt) {
-    p.feed_last = e->pkt_last;
+    p.feed_last = e->feed.last;
   } else {
     p.row_lo = std::max(0, e->next_input_frame - e->cap);
     p.row_hi = e->next_input_frame;

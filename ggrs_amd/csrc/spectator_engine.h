@@ -26,13 +26,9 @@ struct ggrs_spectator_engine {
   ggrs::SpanTimer timer;
   // the packet feed (ggrs_spectator_set_packet_feed, spectator_ingest.hip)
   int32_t pkt = 0;                 // the sessions' inputs and arrivals come from packets
-  int32_t pkt_maxp = 0, pkt_inputs = 0, pkt_stride = 0;
-  int32_t* pkt_last = nullptr;     // [S] the endpoint's last_recv_frame: the session's input window ends here
-  int32_t* pkt_stop = nullptr;     // [S] NULL_FRAME, or the call whose packet stopped the session
-  int32_t* pkt_status = nullptr;   // [cap][S]
-  int32_t* pkt_ack = nullptr;      // [cap][S]
-  uint8_t* pkt_staging = nullptr;  // host packets on their way to the kernel
-  size_t pkt_staging_bytes = 0;
+  int32_t pkt_maxp = 0;            // the hosts' max_prediction
+  ggrs::PacketFeedState feed;      // (last: the session's input window ends here; stop: the call whose packet
+                                   // stopped the session; staged beside the packets: the calls' notes)
 };
 
 namespace ggrs {

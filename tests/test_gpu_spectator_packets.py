@@ -182,6 +182,48 @@ def test_damaged_packets(oracle):
         assert (got["advanced"][feed["stop_call"][s]:, s] == 0).all()
 
 
+def test_both_feeds_agree_on_the_same_packets(oracle):
+    """The damage case's packets go to a packet-fed SpectatorEngine and to a packet-fed P2PEngine whose
+    two remote players are the spectator's two players: the receive side both kernels share
+    (csrc/ingest_device.h) must give every (call, session) the same status and ack, the models'."""
+    from ggrs_amd import P2PEngine
+    from tests import packet_feed_model as PF
+    rows, host_upto, damage, feed = M.damage_case()
+    calls, S = host_upto.shape
+    k = M.DAMAGED
+    # on the models alone: no rule only the P2P feed has fires.  Every input row is added first and
+    # calls <= input_capacity, so every row slot holds its frame; no packet names a frame after its call;
+    # and packet_feed_model's receiver over the same packets gives the spectator model's results.
+    assert calls <= k["cap"] and (feed["ack"] <= np.arange(calls)[:, None]).all()
+    assert set(feed["applied"].values()) == set(M.DAMAGE) and (feed["stop_call"] >= 0).sum() >= 2
+    for s in range(S):
+        r = PF.Receiver(np.zeros((calls, k["P"]), np.uint8), k["mp"], k["W"], feed["stride"], cap=k["cap"],
+                        row_hi=lambda c: calls - 1)
+        for c in range(calls):
+            status, _ = r.receive(c, int(feed["start"][c, s]), feed["packets"][c, s, :feed["length"][c, s]].tobytes())
+            assert (status, r.last) == (feed["status"][c, s], feed["ack"][c, s]), (c, s)
+    spec = feed_engine(S, k["P"], k["cap"], k["mfb"], k["speed"], k["W"], feed["stride"], calls, k["mp"])
+    p2p = P2PEngine(S, num_players=k["P"] + 1, local_players=(0,), max_prediction=k["mp"], remote_latency=1,
+                    input_capacity=k["cap"])
+    p2p.set_arrival_schedule(True)
+    p2p.set_packet_feed(k["W"], feed["stride"])
+    p2p.add_inputs(0, np.zeros((calls, S, k["P"] + 1), np.uint8))
+    done = 0
+    for n in (1, 3, 60, 17, calls - 81):  # (groups of 8 calls, whole and partial)
+        sl = slice(done, done + n)
+        for e in (spec, p2p):
+            e.receive_packets(done, feed["start"][sl], feed["length"][sl], feed["packets"][sl])
+        done += n
+    got_spec, got_p2p = spec.read_packet_results(0, calls), p2p.packet_results(0, calls)
+    for what, x, y in (("status", got_spec[0], got_p2p[0]), ("ack", got_spec[1], got_p2p[1])):
+        bad = np.argwhere(x != y)
+        assert len(bad) == 0, (what, "spectator feed against P2P feed", bad[:4].tolist())
+        bad = np.argwhere(x != feed[what])
+        assert len(bad) == 0, (what, "against the model", bad[:4].tolist())
+    spec.close()
+    p2p.close()
+
+
 # ---- 5. the ingest kernel's staging forms
 
 @pytest.mark.parametrize("P,W,cap,stride", [(2, 16, 64, None), (2, 32, 64, 256), (4, 128, 256, None), (4, 128, 256, 1012)])
