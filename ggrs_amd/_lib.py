@@ -5,6 +5,8 @@ There is no fallback: if the HIP library is missing or fails to load, every entr
 import ctypes
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libggrs_amd.so")
 # timing-experiment builds (tools/exp_build.sh) live in ggrs_amd/exp/; only those may replace the library
@@ -179,6 +181,29 @@ def lib():
                 getattr(L, name).restype = ctypes.c_int
         _lib = L
     return _lib
+
+
+def marshal(arrays, shapes, dtypes, device):
+    """ctypes arguments for a call's arrays (None stays None) -> (args, keep).  device: torch tensors
+    on the engine's device, passed in place -- each must be contiguous, of its shape and dtype; else
+    numpy arrays, converted where needed and checked for their shape (keep holds the converted
+    arrays, which must outlive the call)."""
+    args, keep = [], []
+    for a, shape, dt in zip(arrays, shapes, dtypes):
+        if a is None:
+            args.append(None)
+        elif device:
+            if (not hasattr(a, "data_ptr") or tuple(a.shape) != tuple(shape) or not a.is_contiguous()
+                    or str(a.dtype) != "torch." + dt or not a.is_cuda):
+                raise InvalidRequest(-1, f"device arrays must be contiguous {dt} {shape} on the device")
+            args.append(ctypes.c_void_p(a.data_ptr()))
+        else:
+            a = np.ascontiguousarray(a, dt)
+            if a.shape != tuple(shape):
+                raise InvalidRequest(-1, f"expected shape {shape}, got {a.shape}")
+            keep.append(a)
+            args.append(ctypes.c_void_p(a.ctypes.data))
+    return args, keep
 
 
 def check(rc):

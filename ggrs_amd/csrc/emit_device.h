@@ -1,22 +1,24 @@
 // emit_device.h -- device routines shared by the two send sides of the P2P engine's wire protocol,
 // p2p_emit.hip (a session's endpoint towards its peers) and p2p_spec_emit.hip (its endpoints towards
 // its spectators): the streaming bitfield-rle writer, the bincode framing of an encoded packet row,
-// and the coalesced write-out of a group of packet rows from LDS.  Wire format: see codec.hip.
+// the coalesced write-out of a group of packet rows from LDS, and the fill of the per-session words
+// before the first call.  The host side both units share is p2p_engine.h's PacketEmitState.  (An
+// endpoint's pop, send decision and encode loop stay written in each kernel: through shared inline
+// functions packet emit measured 2-3 % slower per call in every form tried)
+// Wire format: see codec.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "codec_device.h"
 #include "common.h"
+#include "p2p_engine.h"
 
 namespace ggrs {
 namespace {
 
-constexpr int kEmitBlock = 64;  // sessions (threads) per block: one wave
 static_assert(kEmitBlock == 64, "the write-out loop splits a group row index by 6 bits");
-constexpr int kEmitGroup = 8;           // packet rows per session built before a write-out, at most
-constexpr size_t kEmitLds = 64 * 1024;  // a block's packet rows of one group slot (and their lengths) must fit
-constexpr int kEmitHeader = 9;          // input_sizes' tag and encoded_bytes' length before the runs
+constexpr int kEmitHeader = 9;  // input_sizes' tag and encoded_bytes' length before the runs
 
 // bitfield-rle over a byte stream fed one byte at a time, into an LDS row (bounded by `room`:
 // ggrs_codec_max_packet_bytes covers every stream, the bound only keeps a wrong length in the row).
@@ -101,6 +103,18 @@ __device__ inline void emit_write_group(const uint8_t* rows, const int32_t* l_le
       dst[cc] = reinterpret_cast<const uint32_t*>(rows + (size_t)rowi * pitch)[cc];
     }
   }
+}
+
+// The emits' per-session words before the first call: the fields in zero_mask 0, the rest NULL_FRAME
+// ([fields][rows])
+__global__ void emit_fill_kernel(int32_t* st, int64_t rows, int fields, uint32_t zero_mask) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (int64_t)fields * rows) st[i] = (zero_mask >> (int)(i / rows)) & 1u ? 0 : GGRS_NULL_FRAME;
+}
+inline int emit_fill(int32_t* st, size_t rows, int fields, uint32_t zero_mask, hipStream_t stream) {
+  emit_fill_kernel<<<grid_of((int64_t)fields * (int64_t)rows, 256), 256, 0, stream>>>(st, (int64_t)rows, fields, zero_mask);
+  HIP_TRY(hipGetLastError());
+  return GGRS_OK;
 }
 
 }  // namespace

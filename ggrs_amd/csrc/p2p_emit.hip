@@ -46,7 +46,7 @@ constexpr int32_t kNull = GGRS_NULL_FRAME;
 constexpr int kRing = kEmitPending;        // PENDING_OUTPUT_SIZE (protocol.rs:22)
 static_assert((kRing & (kRing - 1)) == 0, "ring slots are frame & (kRing - 1)");
 
-struct EmitParams {
+struct EmitParams {  // (this field order: with the shared EmitCalls block first the kernel measured 1 % slower)
   int64_t S;
   int32_t cap, c0, n, G;
   int32_t maxpend, stride, Pp, pkt;
@@ -207,14 +207,6 @@ __global__ __launch_bounds__(kEmitBlock) void p2p_emit_kernel(EmitParams p) {
 #undef l_len
 }
 
-// every session: nothing acknowledged, nothing pending, the stream open
-__global__ void emit_init_kernel(int32_t* st, int64_t S) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)kEmitFields * S) return;
-  const int f = (int)(i / S);
-  st[i] = (f == kEmitLaBytes || f == kEmitHead || f == kEmitCount || f == kEmitStatus) ? 0 : kNull;
-}
-
 int local_players(const ggrs_p2p_engine* e, uint32_t* lpos) {
   int B = 0;
   uint32_t r = 0;
@@ -239,15 +231,13 @@ int p2p_emit_ll_alloc(ggrs_p2p_engine* e) {
 }
 
 int p2p_emit_free(ggrs_p2p_engine* e) {
-  void* bufs[] = {e->emit_ll, e->emit_ring, e->emit_st, e->emit_staging};
+  void* bufs[] = {e->emit_ll, e->emit_ring, e->emit_st};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   e->emit_ll = nullptr;
   e->emit_ring = nullptr;
   e->emit_st = nullptr;
-  e->emit_staging = nullptr;
-  e->emit_staging_bytes = 0;
-  e->emit = 0;
+  e->emit.release();
   return GGRS_OK;
 }
 
@@ -263,15 +253,7 @@ int ggrs_p2p_set_packet_emit(ggrs_p2p_engine_t* e, int32_t max_pending_inputs, i
   const int B = local_players(e, nullptr);
   if (B < 1 || B >= e->cfg.num_players)
     return set_error(GGRS_E_INVALID, "packet emit needs a local and a remote player");
-  if (max_pending_inputs < 1 || max_pending_inputs > kEmitPending)
-    return set_error(GGRS_E_INVALID, "max_pending_inputs must be in 1..%d (PENDING_OUTPUT_SIZE), got %d", kEmitPending,
-                     max_pending_inputs);
-  const int32_t need = ggrs_codec_max_packet_bytes(B, max_pending_inputs);
-  if (out_stride < need || out_stride % 4)
-    return set_error(GGRS_E_INVALID, "out_stride must be a multiple of 4 and >= ggrs_codec_max_packet_bytes(%d, %d) = %d, got %d",
-                     B, max_pending_inputs, need, out_stride);
-  if (out_stride > 1012 || (size_t)kEmitBlock * (odd_dword_pitch(out_stride) + sizeof(int32_t)) > kEmitLds)
-    return set_error(GGRS_E_INVALID, "out_stride %d is too long (at most 1012)", out_stride);
+  if (int rc = PacketEmitState::check(B, max_pending_inputs, out_stride)) return rc;
   HIP_TRY(hipSetDevice(e->cfg.device));
   const size_t S = (size_t)e->cfg.num_sessions;
   if (int rc = p2p_emit_ll_alloc(e)) return rc;
@@ -280,13 +262,11 @@ int ggrs_p2p_set_packet_emit(ggrs_p2p_engine_t* e, int32_t max_pending_inputs, i
     HIP_TRY(hipMalloc(&e->emit_st, sizeof(int32_t) * (size_t)kEmitFields * S));
   }
   HIP_TRY(hipMemsetAsync(e->emit_ring, 0, sizeof(uint32_t) * (size_t)kEmitPending * S, e->stream));
-  emit_init_kernel<<<grid_of((int64_t)kEmitFields * (int64_t)S, 256), 256, 0, e->stream>>>(e->emit_st, (int64_t)S);
-  HIP_TRY(hipGetLastError());
+  // every session: nothing acknowledged, nothing pending, the stream open
+  constexpr uint32_t kZero = 1u << kEmitLaBytes | 1u << kEmitHead | 1u << kEmitCount | 1u << kEmitStatus;
+  if (int rc = emit_fill(e->emit_st, S, kEmitFields, kZero, e->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  e->emit = 1;
-  e->emit_max = max_pending_inputs;
-  e->emit_stride = out_stride;
-  e->emit_next = 0;
+  e->emit.configure(max_pending_inputs, out_stride);
   return GGRS_OK;
 }
 
@@ -294,99 +274,34 @@ int ggrs_p2p_emit_packets(ggrs_p2p_engine_t* e, int32_t first_call, int32_t n, c
                           const uint8_t* resend, int32_t* start_frame, int32_t* packet_len, int32_t* ack_frame,
                           uint8_t* packets, int32_t on_device) {
   if (!e) return set_error(GGRS_E_INVALID, "null engine");
-  if (!e->sched || !e->emit) return set_error(GGRS_E_STATE, "emitting packets needs ggrs_p2p_set_packet_emit");
-  if (n < 0) return set_error(GGRS_E_INVALID, "n_calls must be >= 0");
-  if (first_call != e->emit_next)
-    return set_error(GGRS_E_INVALID, "packets are emitted in call order, each call once (expected call %d, got %d)",
-                     e->emit_next, first_call);
+  if (!e->sched || !e->emit.on) return set_error(GGRS_E_STATE, "emitting packets needs ggrs_p2p_set_packet_emit");
+  const EmitIo io{ack_in, resend, start_frame, packet_len, ack_frame, packets};
+  EmitCalls c;
+  size_t lds = 0;
+  if (int rc = emit_begin(e, e->emit, 1, io, first_call, n, on_device, &c, &lds)) return rc;  // (a group slot is a call)
   if (n == 0) return GGRS_OK;
-  if (!start_frame || !packet_len || !ack_frame || !packets) return set_error(GGRS_E_INVALID, "null argument");
-  if ((int64_t)first_call + n > e->current_frame)
-    return set_error(GGRS_E_INVALID, "calls up to %d are emitted after they ran (%d calls run)", first_call + n - 1,
-                     e->current_frame);
-  if (first_call < std::max(e->next_input_frame, e->next_arrival_call) - e->cap)
-    return set_error(GGRS_E_INVALID, "call %d is no longer held (the last %d calls' rows are)", first_call, e->cap);
-  if (on_device && ((uintptr_t)packets & 3)) return set_error(GGRS_E_INVALID, "device packets must be dword aligned");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  const size_t S = (size_t)e->cfg.num_sessions, rows = (size_t)n * S, stride = (size_t)e->emit_stride;
-  uint8_t *d_ack_in = nullptr, *d_resend = nullptr, *d_start = nullptr, *d_len = nullptr, *d_ack = nullptr, *d_pk = nullptr;
-  if (!on_device) {  // through the staging buffer: [ack_in][start][len][ack][packets][resend]
-    const size_t bytes = rows * (16 + stride + 1);
-    if (int rc = grow_staging(&e->emit_staging, &e->emit_staging_bytes, bytes)) return rc;
-    d_ack_in = e->emit_staging;
-    d_start = d_ack_in + 4 * rows;
-    d_len = d_start + 4 * rows;
-    d_ack = d_len + 4 * rows;
-    d_pk = d_ack + 4 * rows;
-    d_resend = d_pk + rows * stride;
-    if (ack_in) HIP_TRY(hipMemcpyAsync(d_ack_in, ack_in, 4 * rows, hipMemcpyHostToDevice, e->stream));
-    if (resend) HIP_TRY(hipMemcpyAsync(d_resend, resend, rows, hipMemcpyHostToDevice, e->stream));
-  }
-  EmitParams p;
-  p.S = e->cfg.num_sessions;
-  p.cap = e->cap;
-  p.c0 = first_call;
-  p.n = n;
-  p.maxpend = e->emit_max;
-  p.stride = e->emit_stride;
-  p.Pp = e->Pp;
-  p.pkt = e->pkt;
-  const int B = local_players(e, &p.lpos);
-  p.rmask = ~(uint32_t)e->cfg.local_mask & ((1u << e->cfg.num_players) - 1u);
-  p.inputs = e->inputs;
-  p.ll = e->emit_ll;
-  p.arrive = e->arrive;
-  p.pkt_ack = e->feed.ack;
-  p.events = e->events;
-  p.ring = e->emit_ring;
-  p.st = e->emit_st;
-  if (on_device) {
-    p.ack_in = ack_in;
-    p.resend = resend;
-    p.o_start = start_frame;
-    p.o_len = packet_len;
-    p.o_ack = ack_frame;
-    p.o_packets = packets;
-  } else {
-    p.ack_in = ack_in ? reinterpret_cast<const int32_t*>(d_ack_in) : nullptr;
-    p.resend = resend ? d_resend : nullptr;
-    p.o_start = reinterpret_cast<int32_t*>(d_start);
-    p.o_len = reinterpret_cast<int32_t*>(d_len);
-    p.o_ack = reinterpret_cast<int32_t*>(d_ack);
-    p.o_packets = d_pk;
-  }
-  if (int rc = e->timer.before(e->stream)) return rc;
-  const size_t per_call = (size_t)kEmitBlock * (odd_dword_pitch(p.stride) + sizeof(int32_t));
-  p.G = (int32_t)std::max<size_t>(1, std::min<size_t>({(size_t)kEmitGroup, kEmitLds / per_call, (size_t)n}));
-  const size_t lds = p.G * per_call;
-  const int64_t grid = grid_of(p.S, kEmitBlock);
+  uint32_t lpos = 0;
+  const int B = local_players(e, &lpos);
+  const uint32_t rmask = ~(uint32_t)e->cfg.local_mask & ((1u << e->cfg.num_players) - 1u);
+  const EmitParams p{c.S, c.cap, c.c0, c.n, c.G, c.maxpend, c.stride, c.Pp, c.pkt, lpos, rmask, c.inputs, c.ll, c.arrive,
+                     c.pkt_ack, c.events, c.io.ack_in, c.io.resend, e->emit_ring, e->emit_st, c.io.start, c.io.len, c.io.word,
+                     c.io.packets};
+  const int64_t grid = grid_of(c.S, kEmitBlock);
   switch (B) {
     case 1: p2p_emit_kernel<1><<<grid, kEmitBlock, lds, e->stream>>>(p); break;
     case 2: p2p_emit_kernel<2><<<grid, kEmitBlock, lds, e->stream>>>(p); break;
     default: p2p_emit_kernel<3><<<grid, kEmitBlock, lds, e->stream>>>(p); break;
   }
-  HIP_TRY(hipGetLastError());
-  e->timer.count();
-  if (!on_device) {
-    HIP_TRY(hipMemcpyAsync(start_frame, d_start, 4 * rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(packet_len, d_len, 4 * rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(ack_frame, d_ack, 4 * rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(packets, d_pk, rows * stride, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  e->emit_next = first_call + n;
-  return GGRS_OK;
+  return emit_end(e, e->emit, 1, io, c, on_device);
 }
 
 int ggrs_p2p_read_emit_state(ggrs_p2p_engine_t* e, int32_t* last_acked, int32_t* pending, int32_t* status,
                              int32_t* closed_call) {
   if (!e) return set_error(GGRS_E_INVALID, "null engine");
-  if (!e->sched || !e->emit) return set_error(GGRS_E_STATE, "the emit state exists with ggrs_p2p_set_packet_emit only");
+  if (!e->sched || !e->emit.on) return set_error(GGRS_E_STATE, "the emit state exists with ggrs_p2p_set_packet_emit only");
   HIP_TRY(hipSetDevice(e->cfg.device));
   const size_t S = (size_t)e->cfg.num_sessions;
-  auto rd = [&](int32_t* dst, int f) -> hipError_t {
-    return dst ? hipMemcpyAsync(dst, e->emit_st + (size_t)f * S, 4 * S, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
-  };
+  auto rd = [&](int32_t* dst, int f) { return read_field(dst, e->emit_st, f, S, e->stream); };
   HIP_TRY(rd(last_acked, kEmitLaFrame));
   HIP_TRY(rd(pending, kEmitCount));
   HIP_TRY(rd(status, kEmitStatus));

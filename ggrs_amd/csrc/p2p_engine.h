@@ -2,15 +2,143 @@
 // desync detection, lockstep) and p2p_sched.hip (scheduled arrivals: per-session remote-arrival
 // tables, the prediction threshold and disconnects) and p2p_ingest.hip (the packet feed of the
 // scheduled mode) and p2p_emit.hip (its send side) and p2p_spec_emit.hip (the send side towards the
-// sessions' spectators).  Host-side only; no kernels here.
+// sessions' spectators), with the host side the two send sides share (PacketEmitState: configuration
+// and call-order checks, the staging of a launch's arrays, the group plan; emit_begin / emit_end: an
+// emit call before and after the unit's kernel launch; EmitCalls: what emit_begin hands the unit for
+// its kernel's parameters).  Host code and plain structs only; no kernels here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <vector>
 
+#include "codec_device.h"
 #include "common.h"
 #include "p2p_plan.h"
+
+namespace ggrs {
+// the two emits: PENDING_OUTPUT_SIZE (protocol.rs:22); the kernels' block (one wave of sessions), the
+// packet rows per session built before a write-out (at most), and the LDS a block's rows of one group
+// slot (and their lengths) must fit
+constexpr int kEmitPending = 128;
+constexpr int kEmitBlock = 64;
+constexpr int kEmitGroup = 8;
+constexpr size_t kEmitLds = 64 * 1024;
+
+// The six arrays of an emit launch of n calls, K endpoints a session (packet emit: K = 1)
+struct EmitIo {
+  const int32_t* ack_in;  // [n][K][S] or null
+  const uint8_t* resend;  // [n][K][S] or null
+  int32_t* start;         // [n][K][S]
+  int32_t* len;           // [n][K][S]
+  int32_t* word;          // [n][S] the per-call word: packet emit's ack_frame, spectator emit's notes
+  uint8_t* packets;       // [n][K][S][stride]
+};
+
+// The host side of an emit (ggrs_p2p_set_packet_emit, ggrs_p2p_set_spectator_emit): its configuration,
+// the next call to emit and the staging buffer of host-sourced calls; embedded twice in the engine.
+struct PacketEmitState {
+  int32_t on = 0;           // the mode
+  int32_t max_pending = 0;  // max_pending_inputs
+  int32_t stride = 0;       // bytes per emitted packet row
+  int32_t next = 0;         // the next call to emit
+  uint8_t* staging = nullptr;  // host-sourced calls: acks, resend flags and the outputs
+  size_t staging_bytes = 0;
+
+  // LDS of one group slot: a block's packet rows and their lengths
+  static size_t slot_bytes(int32_t stride) { return (size_t)kEmitBlock * (odd_dword_pitch(stride) + sizeof(int32_t)); }
+  // max_pending_inputs and out_stride for pending inputs of `bytes` bytes
+  static int check(int bytes, int32_t max_pending_inputs, int32_t out_stride) {
+    if (max_pending_inputs < 1 || max_pending_inputs > kEmitPending)
+      return set_error(GGRS_E_INVALID, "max_pending_inputs must be in 1..%d (PENDING_OUTPUT_SIZE), got %d", kEmitPending,
+                       max_pending_inputs);
+    const int32_t need = ggrs_codec_max_packet_bytes(bytes, max_pending_inputs);
+    if (out_stride < need || out_stride % 4)
+      return set_error(GGRS_E_INVALID, "out_stride must be a multiple of 4 and >= ggrs_codec_max_packet_bytes(%d, %d) = %d, got %d",
+                       bytes, max_pending_inputs, need, out_stride);
+    if (out_stride > 1012 || slot_bytes(out_stride) > kEmitLds)
+      return set_error(GGRS_E_INVALID, "out_stride %d is too long (at most 1012)", out_stride);
+    return GGRS_OK;
+  }
+  void configure(int32_t max_pending_inputs, int32_t out_stride) {
+    on = 1;
+    max_pending = max_pending_inputs;
+    stride = out_stride;
+    next = 0;
+  }
+  // An emit call's order and arguments: calls first_call .. first_call + n - 1 of current_frame calls
+  // run, the input rows held from call oldest_held on (the last cap).  n == 0 is GGRS_OK with nothing
+  // to launch.
+  int check_calls(int32_t first_call, int32_t n, int32_t current_frame, int32_t oldest_held, int32_t cap, const EmitIo& io,
+                  int32_t on_device) const {
+    if (n < 0) return set_error(GGRS_E_INVALID, "n_calls must be >= 0");
+    if (first_call != next)
+      return set_error(GGRS_E_INVALID, "packets are emitted in call order, each call once (expected call %d, got %d)", next,
+                       first_call);
+    if (n == 0) return GGRS_OK;
+    if (!io.start || !io.len || !io.word || !io.packets) return set_error(GGRS_E_INVALID, "null argument");
+    if ((int64_t)first_call + n > current_frame)
+      return set_error(GGRS_E_INVALID, "calls up to %d are emitted after they ran (%d calls run)", first_call + n - 1,
+                       current_frame);
+    if (first_call < oldest_held)
+      return set_error(GGRS_E_INVALID, "call %d is no longer held (the last %d calls' rows are)", first_call, cap);
+    if (on_device && ((uintptr_t)io.packets & 3)) return set_error(GGRS_E_INVALID, "device packets must be dword aligned");
+    return GGRS_OK;
+  }
+  // The arrays the kernel takes for the caller's `io`: the caller's own when they are on the device,
+  // else the staging buffer's, [ack_in][start][len][word][packets][resend], the two inputs uploaded
+  // where given (stream order keeps an earlier launch's use of the buffer ahead of the copies).
+  int begin(const EmitIo& io, size_t n, size_t K, size_t S, int32_t on_device, hipStream_t stream, EmitIo* dev) {
+    *dev = io;
+    if (on_device) return GGRS_OK;
+    const size_t rows = n * K * S, calls = n * S;
+    if (int rc = grow_staging(&staging, &staging_bytes, rows * (12 + (size_t)stride + 1) + 4 * calls)) return rc;
+    int32_t* d_ack_in = reinterpret_cast<int32_t*>(staging);
+    dev->start = d_ack_in + rows;
+    dev->len = dev->start + rows;
+    dev->word = dev->len + rows;
+    dev->packets = reinterpret_cast<uint8_t*>(dev->word + calls);
+    uint8_t* d_resend = dev->packets + rows * (size_t)stride;
+    if (io.ack_in) HIP_TRY(hipMemcpyAsync(d_ack_in, io.ack_in, 4 * rows, hipMemcpyHostToDevice, stream));
+    if (io.resend) HIP_TRY(hipMemcpyAsync(d_resend, io.resend, rows, hipMemcpyHostToDevice, stream));
+    dev->ack_in = io.ack_in ? d_ack_in : nullptr;
+    dev->resend = io.resend ? d_resend : nullptr;
+    return GGRS_OK;
+  }
+  // ... and after the launch: the staged outputs back into the caller's, waited for
+  int end(const EmitIo& io, const EmitIo& dev, size_t n, size_t K, size_t S, int32_t on_device, hipStream_t stream) const {
+    if (on_device) return GGRS_OK;
+    const size_t rows = n * K * S;
+    HIP_TRY(hipMemcpyAsync(io.start, dev.start, 4 * rows, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(io.len, dev.len, 4 * rows, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(io.word, dev.word, 4 * n * S, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(io.packets, dev.packets, rows * (size_t)stride, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return GGRS_OK;
+  }
+  // The group slots built before a write-out and the launch's dynamic LDS, for n calls of
+  // slots_per_call (call, endpoint) pairs: up to kEmitGroup calls' slots, as many as fit the LDS
+  // budget, which keeps two blocks on a CU at every stride
+  struct Group { int32_t G; size_t lds; };
+  Group group(size_t slots_per_call, size_t n) const {
+    const size_t per_slot = slot_bytes(stride);
+    const size_t G = std::max<size_t>(1, std::min<size_t>({kEmitGroup * slots_per_call, kEmitLds / per_slot, n * slots_per_call}));
+    return {(int32_t)G, G * per_slot};
+  }
+  void release() {
+    if (staging) (void)hipFree(staging);
+    staging = nullptr;
+    staging_bytes = 0;
+    on = 0;
+  }
+};
+
+// Field f of a [fields][rows] device array into a host array, if one is given
+inline hipError_t read_field(int32_t* dst, const int32_t* fields, int f, size_t rows, hipStream_t stream) {
+  return dst ? hipMemcpyAsync(dst, fields + (size_t)f * rows, 4 * rows, hipMemcpyDeviceToHost, stream) : hipSuccess;
+}
+}  // namespace ggrs
 
 struct ggrs_p2p_engine {
   ggrs_p2p_config_t cfg{};
@@ -70,36 +198,24 @@ struct ggrs_p2p_engine {
   int32_t pkt = 0;                 // the mode
   ggrs::PacketFeedState feed;      // (stop: see p2p_ingest.hip; staged beside the packets: the calls' events)
   // packet emit (ggrs_p2p_set_packet_emit; p2p_emit.hip): the sessions' outgoing Input messages
-  int32_t emit = 0;                 // the mode
-  int32_t emit_max = 0;             // max_pending_inputs
-  int32_t emit_stride = 0;          // bytes per emitted packet row
-  int32_t emit_next = 0;            // the next call to emit
+  ggrs::PacketEmitState emit;
   int32_t* emit_ll = nullptr;       // [cap][S] per call: the local players' last queued frame after it, or
                                     // kEmitStopped from the call that stopped the session (the scheduled kernels write it)
   uint32_t* emit_ring = nullptr;    // [kEmitPending][S] pending_output, slot frame % kEmitPending
   int32_t* emit_st = nullptr;       // [kEmitFields][S] the endpoint's send-side words (EmitField)
-  uint8_t* emit_staging = nullptr;  // host-sourced calls: acks, resend flags and the outputs
-  size_t emit_staging_bytes = 0;
   // spectator emit (ggrs_p2p_set_spectator_emit; p2p_spec_emit.hip): the sessions' confirmed inputs as
   // Input messages to their spectators, spec_k endpoints per session; reads emit_ll as packet emit does
-  int32_t spec = 0;                 // the mode
+  ggrs::PacketEmitState spec;
   int32_t spec_k = 0;               // spectator endpoints per session
-  int32_t spec_max = 0;             // max_pending_inputs
-  int32_t spec_stride = 0;          // bytes per emitted packet row
   int32_t spec_q = 0;               // frames of the confirmed-input ring (2^k)
-  int32_t spec_next = 0;            // the next call to emit
   uint32_t* spec_ring = nullptr;    // [spec_q][S] every player's confirmed byte of frame f, slot f & (spec_q - 1)
   int32_t* spec_st = nullptr;       // [kSpecFields][S] the session's words (SpecField)
   int32_t* spec_ep = nullptr;       // [kSpecEpFields][spec_k][S] the endpoints' words (SpecEpField)
-  uint8_t* spec_staging = nullptr;  // host-sourced calls: acks, resend flags and the outputs
-  size_t spec_staging_bytes = 0;
   ggrs::SpanTimer timer;
 };
 
 namespace ggrs {
-// packet emit: PENDING_OUTPUT_SIZE (protocol.rs:22); the mark of a stopped session in emit_ll; the
-// per-session words kept between launches
-constexpr int kEmitPending = 128;
+// packet emit: the mark of a stopped session in emit_ll; the per-session words kept between launches
 constexpr int32_t kEmitStopped = INT32_MIN;
 enum EmitField : int {
   kEmitLaFrame = 0,  // last_acked_input: its frame
@@ -136,6 +252,46 @@ int p2p_emit_free(ggrs_p2p_engine* e);
 int p2p_spec_emit_free(ggrs_p2p_engine* e);
 // emit_ll, shared by the two emits: allocated by the first configured, every row "nothing queued"
 int p2p_emit_ll_alloc(ggrs_p2p_engine* e);
+
+// What an emit kernel's parameters take from the engine for a launch of calls c0 .. c0 + n - 1: the
+// rows the scheduled kernels and the feed left, the emit's configuration and the launch's arrays
+// (device pointers)
+struct EmitCalls {
+  int64_t S;
+  int32_t cap, c0, n;
+  int32_t G;               // group slots (PacketEmitState::group)
+  int32_t maxpend, stride, Pp, pkt;
+  const uint8_t* inputs;   // [cap][S] row words
+  const int32_t* ll;       // [cap][S] the local players' last queued frame after the call, or kEmitStopped
+  const int32_t* arrive;   // [cap][S] (the packet feed off)
+  const int32_t* pkt_ack;  // [cap][S] (the packet feed on)
+  const uint8_t* events;   // [cap][S]
+  EmitIo io;
+};
+
+// An emit call of either kind, of K endpoints a session over the engine's `st`.  emit_begin: the
+// call-order checks, then (n > 0) the staging, *c filled and the launch's dynamic LDS bytes; the unit
+// launches its kernel on grid_of(c->S, kEmitBlock) blocks; emit_end: the copy back, the call counted.
+inline int emit_begin(ggrs_p2p_engine* e, PacketEmitState& st, size_t K, const EmitIo& io, int32_t first_call, int32_t n,
+                      int32_t on_device, EmitCalls* c, size_t* lds) {
+  const int32_t oldest_held = std::max(e->next_input_frame, e->next_arrival_call) - e->cap;
+  if (int rc = st.check_calls(first_call, n, e->current_frame, oldest_held, e->cap, io, on_device)) return rc;
+  if (n == 0) return GGRS_OK;
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  const auto grp = st.group(K, n);
+  *c = {e->cfg.num_sessions, e->cap, first_call, n, grp.G, st.max_pending, st.stride, e->Pp, e->pkt, e->inputs,
+        e->emit_ll, e->arrive, e->feed.ack, e->events, {}};
+  *lds = grp.lds;
+  if (int rc = st.begin(io, n, K, (size_t)c->S, on_device, e->stream, &c->io)) return rc;
+  return e->timer.before(e->stream);
+}
+inline int emit_end(ggrs_p2p_engine* e, PacketEmitState& st, size_t K, const EmitIo& io, const EmitCalls& c, int32_t on_device) {
+  HIP_TRY(hipGetLastError());
+  e->timer.count();
+  if (int rc = st.end(io, c.io, c.n, K, (size_t)c.S, on_device, e->stream)) return rc;
+  st.next = c.c0 + c.n;
+  return GGRS_OK;
+}
 // p2p_sched.hip: enable scheduled mode (allocate and initialise its buffers), run n calls, upload arrival rows
 int p2p_sched_enable(ggrs_p2p_engine* e);
 int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n);

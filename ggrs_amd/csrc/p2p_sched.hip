@@ -1845,7 +1845,7 @@ int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n) {
   p.trace = e->trace;
   p.trace_cap = e->trace ? e->cfg.trace_capacity : 0;
   p.emit_ll = e->emit_ll;
-  p.emit = e->emit || e->spec;  // (spectator emit reads the same row)
+  p.emit = e->emit.on || e->spec.on;  // (spectator emit reads the same row)
   SchedPlanIn in{};
   in.sessions = p.S;
   in.players = e->cfg.num_players;
@@ -1897,8 +1897,8 @@ int ggrs_p2p_set_arrival_schedule(ggrs_p2p_engine_t* e, int32_t on) {
   if (!on) {
     e->sched = 0;
     e->pkt = 0;  // (the packet feed is a form of the arrival schedules)
-    e->emit = 0;  // (and so is packet emit)
-    e->spec = 0;  // (and spectator emit)
+    e->emit.on = 0;  // (and so is packet emit)
+    e->spec.on = 0;  // (and spectator emit)
     return GGRS_OK;
   }
   if (e->cfg.max_prediction + e->cfg.input_delay + 2 >= kQ)
@@ -1959,7 +1959,7 @@ int ggrs_p2p_add_arrivals(ggrs_p2p_engine_t* e, int32_t first_call, int32_t n, c
 int ggrs_p2p_add_peer_reports(ggrs_p2p_engine_t* e, int32_t first_call, int32_t n, const int32_t* reports) {
   if (!e || (!reports && n > 0)) return set_error(GGRS_E_INVALID, "null argument");
   if (!e->sched) return set_error(GGRS_E_STATE, "peer reports need ggrs_p2p_set_arrival_schedule(e, 1)");
-  if (e->spec)
+  if (e->spec.on)
     return set_error(GGRS_E_STATE, "peer reports with spectator emit are not supported (the emit restates the connect "
                                    "status from the events alone)");
   if (n < 0 || first_call < e->current_frame || first_call + n > e->next_arrival_call)

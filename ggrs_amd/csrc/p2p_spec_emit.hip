@@ -362,20 +362,6 @@ __global__ __launch_bounds__(kEmitBlock) void p2p_spec_emit_kernel(SpecParams p)
 #undef l_len
 }
 
-// every session: nothing confirmed yet, every player connected; every endpoint: nothing
-// acknowledged, nothing pending, the stream open
-__global__ void spec_init_kernel(int32_t* st, int32_t* ep, int64_t S, int K) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < (int64_t)kSpecFields * S) {
-    const int f = (int)(i / S);
-    st[i] = (f == kSpecNext || f == kSpecDisc) ? 0 : kNull;
-  }
-  if (i < (int64_t)kSpecEpFields * K * S) {
-    const int f = (int)(i / (K * S));
-    ep[i] = (f == kSpecEpLaFrame || f == kSpecEpClosedCall) ? kNull : 0;
-  }
-}
-
 // GGRS_SPEC_EMIT_DEDUP=0 encodes every endpoint's packet on its own (for the comparison; default 1)
 int32_t spec_dedup_from_env() {
   const char* v = std::getenv("GGRS_SPEC_EMIT_DEDUP");
@@ -387,15 +373,13 @@ int32_t spec_dedup_from_env() {
 namespace ggrs {
 
 int p2p_spec_emit_free(ggrs_p2p_engine* e) {
-  void* bufs[] = {e->spec_ring, e->spec_st, e->spec_ep, e->spec_staging};
+  void* bufs[] = {e->spec_ring, e->spec_st, e->spec_ep};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   e->spec_ring = nullptr;
   e->spec_st = nullptr;
   e->spec_ep = nullptr;
-  e->spec_staging = nullptr;
-  e->spec_staging_bytes = 0;
-  e->spec = 0;
+  e->spec.release();
   return GGRS_OK;
 }
 
@@ -416,15 +400,7 @@ int ggrs_p2p_set_spectator_emit(ggrs_p2p_engine_t* e, int32_t num_spectators, in
     return set_error(GGRS_E_INVALID, "spectator emit needs a local player (the session that hosts the spectators)");
   if (num_spectators < 1 || num_spectators > 4)
     return set_error(GGRS_E_INVALID, "num_spectators must be in 1..4, got %d", num_spectators);
-  if (max_pending_inputs < 1 || max_pending_inputs > kEmitPending)
-    return set_error(GGRS_E_INVALID, "max_pending_inputs must be in 1..%d (PENDING_OUTPUT_SIZE), got %d", kEmitPending,
-                     max_pending_inputs);
-  const int32_t need = ggrs_codec_max_packet_bytes(P, max_pending_inputs);
-  if (out_stride < need || out_stride % 4)
-    return set_error(GGRS_E_INVALID, "out_stride must be a multiple of 4 and >= ggrs_codec_max_packet_bytes(%d, %d) = %d, got %d",
-                     P, max_pending_inputs, need, out_stride);
-  if (out_stride > 1012 || (size_t)kEmitBlock * (odd_dword_pitch(out_stride) + sizeof(int32_t)) > kEmitLds)
-    return set_error(GGRS_E_INVALID, "out_stride %d is too long (at most 1012)", out_stride);
+  if (int rc = PacketEmitState::check(P, max_pending_inputs, out_stride)) return rc;
   HIP_TRY(hipSetDevice(e->cfg.device));
   const size_t S = (size_t)e->cfg.num_sessions, K = (size_t)num_spectators;
   // the ring holds the slowest open endpoint's pending frames, its last_acked, and the frames queued
@@ -444,16 +420,15 @@ int ggrs_p2p_set_spectator_emit(ggrs_p2p_engine_t* e, int32_t num_spectators, in
     HIP_TRY(hipMalloc(&e->spec_ep, sizeof(int32_t) * (size_t)kSpecEpFields * K * S));
   }
   HIP_TRY(hipMemsetAsync(e->spec_ring, 0, sizeof(uint32_t) * (size_t)Q * S, e->stream));
-  const int64_t cells = (int64_t)std::max<size_t>(kSpecFields, kSpecEpFields * K) * (int64_t)S;
-  spec_init_kernel<<<grid_of(cells, 256), 256, 0, e->stream>>>(e->spec_st, e->spec_ep, (int64_t)S, (int)K);
-  HIP_TRY(hipGetLastError());
+  // every session: nothing confirmed yet, every player connected; every endpoint: nothing
+  // acknowledged, nothing pending, the stream open
+  if (int rc = emit_fill(e->spec_st, S, kSpecFields, 1u << kSpecNext | 1u << kSpecDisc, e->stream)) return rc;
+  constexpr uint32_t kEpZero = 1u << kSpecEpLaBytes | 1u << kSpecEpPending | 1u << kSpecEpStatus;
+  if (int rc = emit_fill(e->spec_ep, K * S, kSpecEpFields, kEpZero, e->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  e->spec = 1;
+  e->spec.configure(max_pending_inputs, out_stride);
   e->spec_k = (int32_t)K;
-  e->spec_max = max_pending_inputs;
-  e->spec_stride = out_stride;
   e->spec_q = Q;
-  e->spec_next = 0;
   return GGRS_OK;
 }
 
@@ -461,110 +436,36 @@ int ggrs_p2p_emit_spectator_packets(ggrs_p2p_engine_t* e, int32_t first_call, in
                                     const uint8_t* resend, int32_t* start_frame, int32_t* packet_len, int32_t* notes,
                                     uint8_t* packets, int32_t on_device) {
   if (!e) return set_error(GGRS_E_INVALID, "null engine");
-  if (!e->sched || !e->spec) return set_error(GGRS_E_STATE, "emitting spectator packets needs ggrs_p2p_set_spectator_emit");
-  if (n < 0) return set_error(GGRS_E_INVALID, "n_calls must be >= 0");
-  if (first_call != e->spec_next)
-    return set_error(GGRS_E_INVALID, "packets are emitted in call order, each call once (expected call %d, got %d)",
-                     e->spec_next, first_call);
+  if (!e->sched || !e->spec.on) return set_error(GGRS_E_STATE, "emitting spectator packets needs ggrs_p2p_set_spectator_emit");
+  const EmitIo io{ack_in, resend, start_frame, packet_len, notes, packets};
+  EmitCalls c;
+  size_t lds = 0;
+  // (a group slot is a (call, endpoint) pair)
+  if (int rc = emit_begin(e, e->spec, (size_t)e->spec_k, io, first_call, n, on_device, &c, &lds)) return rc;
   if (n == 0) return GGRS_OK;
-  if (!start_frame || !packet_len || !notes || !packets) return set_error(GGRS_E_INVALID, "null argument");
-  if ((int64_t)first_call + n > e->current_frame)
-    return set_error(GGRS_E_INVALID, "calls up to %d are emitted after they ran (%d calls run)", first_call + n - 1,
-                     e->current_frame);
-  if (first_call < std::max(e->next_input_frame, e->next_arrival_call) - e->cap)
-    return set_error(GGRS_E_INVALID, "call %d is no longer held (the last %d calls' rows are)", first_call, e->cap);
-  if (on_device && ((uintptr_t)packets & 3)) return set_error(GGRS_E_INVALID, "device packets must be dword aligned");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  const size_t S = (size_t)e->cfg.num_sessions, K = (size_t)e->spec_k, rows = (size_t)n * K * S;
-  const size_t stride = (size_t)e->spec_stride, nS = (size_t)n * S;
-  uint8_t *d_ack_in = nullptr, *d_resend = nullptr, *d_start = nullptr, *d_len = nullptr, *d_notes = nullptr, *d_pk = nullptr;
-  if (!on_device) {  // through the staging buffer: [ack_in][start][len][notes][packets][resend]
-    const size_t bytes = rows * (12 + stride + 1) + 4 * nS;
-    if (int rc = grow_staging(&e->spec_staging, &e->spec_staging_bytes, bytes)) return rc;
-    d_ack_in = e->spec_staging;
-    d_start = d_ack_in + 4 * rows;
-    d_len = d_start + 4 * rows;
-    d_notes = d_len + 4 * rows;
-    d_pk = d_notes + 4 * nS;
-    d_resend = d_pk + rows * stride;
-    if (ack_in) HIP_TRY(hipMemcpyAsync(d_ack_in, ack_in, 4 * rows, hipMemcpyHostToDevice, e->stream));
-    if (resend) HIP_TRY(hipMemcpyAsync(d_resend, resend, rows, hipMemcpyHostToDevice, e->stream));
-  }
-  SpecParams p;
-  p.S = e->cfg.num_sessions;
-  p.cap = e->cap;
-  p.c0 = first_call;
-  p.n = n;
-  p.K = e->spec_k;
-  p.maxpend = e->spec_max;
-  p.stride = e->spec_stride;
-  p.Pp = e->Pp;
-  p.pkt = e->pkt;
-  p.dedup = spec_dedup_from_env();
-  p.qmask = (uint32_t)e->spec_q - 1u;
-  p.lmask = (uint32_t)e->cfg.local_mask & ((1u << e->cfg.num_players) - 1u);
-  p.inputs = e->inputs;
-  p.row_tag = e->row_tag;
-  p.ll = e->emit_ll;
-  p.arrive = e->arrive;
-  p.pkt_ack = e->feed.ack;
-  p.events = e->events;
-  p.ring = e->spec_ring;
-  p.st = e->spec_st;
-  p.ep = e->spec_ep;
-  if (on_device) {
-    p.ack_in = ack_in;
-    p.resend = resend;
-    p.o_start = start_frame;
-    p.o_len = packet_len;
-    p.o_notes = notes;
-    p.o_packets = packets;
-  } else {
-    p.ack_in = ack_in ? reinterpret_cast<const int32_t*>(d_ack_in) : nullptr;
-    p.resend = resend ? d_resend : nullptr;
-    p.o_start = reinterpret_cast<int32_t*>(d_start);
-    p.o_len = reinterpret_cast<int32_t*>(d_len);
-    p.o_notes = reinterpret_cast<int32_t*>(d_notes);
-    p.o_packets = d_pk;
-  }
-  if (int rc = e->timer.before(e->stream)) return rc;
-  // the rows of one (call, endpoint) pair are a group slot; up to 8 calls' slots, as many as fit the
-  // LDS budget, which keeps two blocks on a CU at every stride
-  const size_t per_slot = (size_t)kEmitBlock * (odd_dword_pitch(p.stride) + sizeof(int32_t));
-  p.G = (int32_t)std::max<size_t>(1, std::min<size_t>({(size_t)kEmitGroup * K, kEmitLds / per_slot, (size_t)n * K}));
-  const size_t lds = p.G * per_slot;
-  const int64_t grid = grid_of(p.S, kEmitBlock);
+  const uint32_t lmask = (uint32_t)e->cfg.local_mask & ((1u << e->cfg.num_players) - 1u);
+  const SpecParams p{c.S, c.cap, c.c0, c.n, c.G, e->spec_k, c.maxpend, c.stride, c.Pp, c.pkt, spec_dedup_from_env(),
+                     (uint32_t)e->spec_q - 1u, lmask, c.inputs, e->row_tag, c.ll, c.arrive, c.pkt_ack, c.events, c.io.ack_in,
+                     c.io.resend, e->spec_ring, e->spec_st, e->spec_ep, c.io.start, c.io.len, c.io.word, c.io.packets};
+  const int64_t grid = grid_of(c.S, kEmitBlock);
   switch (e->cfg.num_players) {
     case 1: p2p_spec_emit_kernel<1><<<grid, kEmitBlock, lds, e->stream>>>(p); break;
     case 2: p2p_spec_emit_kernel<2><<<grid, kEmitBlock, lds, e->stream>>>(p); break;
     case 3: p2p_spec_emit_kernel<3><<<grid, kEmitBlock, lds, e->stream>>>(p); break;
     default: p2p_spec_emit_kernel<4><<<grid, kEmitBlock, lds, e->stream>>>(p); break;
   }
-  HIP_TRY(hipGetLastError());
-  e->timer.count();
-  if (!on_device) {
-    HIP_TRY(hipMemcpyAsync(start_frame, d_start, 4 * rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(packet_len, d_len, 4 * rows, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(notes, d_notes, 4 * nS, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(packets, d_pk, rows * stride, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  e->spec_next = first_call + n;
-  return GGRS_OK;
+  return emit_end(e, e->spec, (size_t)e->spec_k, io, c, on_device);
 }
 
 int ggrs_p2p_read_spectator_emit_state(ggrs_p2p_engine_t* e, int32_t* next_spectator_frame, int32_t* last_acked,
                                        int32_t* pending, int32_t* status, int32_t* closed_call) {
   if (!e) return set_error(GGRS_E_INVALID, "null engine");
-  if (!e->sched || !e->spec)
+  if (!e->sched || !e->spec.on)
     return set_error(GGRS_E_STATE, "the spectator emit state exists with ggrs_p2p_set_spectator_emit only");
   HIP_TRY(hipSetDevice(e->cfg.device));
   const size_t S = (size_t)e->cfg.num_sessions, KS = (size_t)e->spec_k * S;
-  if (next_spectator_frame)
-    HIP_TRY(hipMemcpyAsync(next_spectator_frame, e->spec_st + (size_t)kSpecNext * S, 4 * S, hipMemcpyDeviceToHost, e->stream));
-  auto rd = [&](int32_t* dst, int f) -> hipError_t {
-    return dst ? hipMemcpyAsync(dst, e->spec_ep + (size_t)f * KS, 4 * KS, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
-  };
+  HIP_TRY(read_field(next_spectator_frame, e->spec_st, kSpecNext, S, e->stream));
+  auto rd = [&](int32_t* dst, int f) { return read_field(dst, e->spec_ep, f, KS, e->stream); };
   HIP_TRY(rd(last_acked, kSpecEpLaFrame));
   HIP_TRY(rd(pending, kSpecEpPending));
   HIP_TRY(rd(status, kSpecEpStatus));

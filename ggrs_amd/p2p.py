@@ -312,27 +312,9 @@ class P2PEngine:
         arrays, or torch tensors on the engine's device (read in place by the launch)."""
         n, S = int(start_frame.shape[0]), self.num_sessions
         stride = getattr(self, "packet_stride", None) or int(packets.shape[-1])
-        shapes = ((n, S), (n, S), (n, S, stride), (n, S))
-        dtypes = ("int32", "int32", "uint8", "uint8")
-        arrs = [start_frame, packet_len, packets, events]
         dev = hasattr(packets, "data_ptr")
-        ptrs = []
-        for a, shape, dt in zip(arrs, shapes, dtypes):
-            if a is None:
-                ptrs.append(None)
-                continue
-            if dev:
-                if tuple(a.shape) != shape or not a.is_contiguous() or str(a.dtype) != "torch." + dt or not a.is_cuda:
-                    raise InvalidRequest(-1, f"device arrays must be contiguous {dt} {shape} on the device")
-                ptrs.append(ctypes.c_void_p(a.data_ptr()))
-            else:
-                a = np.ascontiguousarray(a, dt)
-                if a.shape != shape:
-                    raise InvalidRequest(-1, f"expected shape {shape}, got {a.shape}")
-                ptrs.append(a)
-        if not dev:
-            keep = ptrs
-            ptrs = [_vp(a) for a in keep]
+        ptrs, keep = _lib.marshal((start_frame, packet_len, packets, events), ((n, S), (n, S), (n, S, stride), (n, S)),
+                                  ("int32", "int32", "uint8", "uint8"), dev)
         _lib.check(self._L.ggrs_p2p_receive_packets(self._h, first_call, n, *ptrs, int(dev)))
 
     def packet_results(self, first_call, n_calls):
@@ -367,31 +349,16 @@ class P2PEngine:
         stride = getattr(self, "out_stride", None)
         if stride is None:
             _lib.check(self._L.ggrs_p2p_emit_packets(self._h, first_call, n, None, None, None, None, None, None, 0))
-        dev = out is not None
         shapes = ((n, S), (n, S), (n, S), (n, S), (n, S), (n, S, stride))
+        return self._emit(self._L.ggrs_p2p_emit_packets, first_call, n, ack_in, resend, out, shapes)
+
+    def _emit(self, entry, first_call, n, ack_in, resend, out, shapes):
+        """An emit call of either kind: [ack_in, resend, start, len, per-call word, packets]."""
         dtypes = ("int32", "uint8", "int32", "int32", "int32", "uint8")
-        if dev:
-            arrs = [ack_in, resend] + list(out)
-            ptrs = []
-            for a, shape, dt in zip(arrs, shapes, dtypes):
-                if a is None:
-                    ptrs.append(None)
-                    continue
-                if (not hasattr(a, "data_ptr") or tuple(a.shape) != shape or not a.is_contiguous()
-                        or str(a.dtype) != "torch." + dt or not a.is_cuda):
-                    raise InvalidRequest(-1, f"device arrays must be contiguous {dt} {shape} on the device")
-                ptrs.append(ctypes.c_void_p(a.data_ptr()))
-            _lib.check(self._L.ggrs_p2p_emit_packets(self._h, first_call, n, *ptrs, 1))
-            return tuple(out)
-        ins = []
-        for a, shape, dt in zip((ack_in, resend), shapes, dtypes):
-            if a is not None:
-                a = np.ascontiguousarray(a, dt)
-                if a.shape != shape:
-                    raise InvalidRequest(-1, f"expected shape {shape}, got {a.shape}")
-            ins.append(a)
-        outs = [np.zeros(shape, dt) for shape, dt in zip(shapes[2:], dtypes[2:])]
-        _lib.check(self._L.ggrs_p2p_emit_packets(self._h, first_call, n, *(_vp(a) for a in ins + outs), 0))
+        dev = out is not None
+        outs = list(out) if dev else [np.zeros(shape, dt) for shape, dt in zip(shapes[2:], dtypes[2:])]
+        ptrs, keep = _lib.marshal([ack_in, resend] + outs, shapes, dtypes, dev)
+        _lib.check(entry(self._h, first_call, n, *ptrs, int(dev)))
         return tuple(outs)
 
     def emit_state(self):
@@ -428,31 +395,8 @@ class P2PEngine:
             _lib.check(self._L.ggrs_p2p_emit_spectator_packets(self._h, first_call, n, None, None, None, None, None,
                                                                None, 0))  # (the library's own error)
             raise _lib.GgrsError(_lib.GGRS_E_STATE, "emit_spectator_packets needs set_spectator_emit")
-        dev = out is not None
         shapes = ((n, K, S), (n, K, S), (n, K, S), (n, K, S), (n, S), (n, K, S, stride))
-        dtypes = ("int32", "uint8", "int32", "int32", "int32", "uint8")
-        if dev:
-            ptrs = []
-            for a, shape, dt in zip([ack_in, resend] + list(out), shapes, dtypes):
-                if a is None:
-                    ptrs.append(None)
-                    continue
-                if (not hasattr(a, "data_ptr") or tuple(a.shape) != shape or not a.is_contiguous()
-                        or str(a.dtype) != "torch." + dt or not a.is_cuda):
-                    raise InvalidRequest(-1, f"device arrays must be contiguous {dt} {shape} on the device")
-                ptrs.append(ctypes.c_void_p(a.data_ptr()))
-            _lib.check(self._L.ggrs_p2p_emit_spectator_packets(self._h, first_call, n, *ptrs, 1))
-            return tuple(out)
-        ins = []
-        for a, shape, dt in zip((ack_in, resend), shapes, dtypes):
-            if a is not None:
-                a = np.ascontiguousarray(a, dt)
-                if a.shape != shape:
-                    raise InvalidRequest(-1, f"expected shape {shape}, got {a.shape}")
-            ins.append(a)
-        outs = [np.zeros(shape, dt) for shape, dt in zip(shapes[2:], dtypes[2:])]
-        _lib.check(self._L.ggrs_p2p_emit_spectator_packets(self._h, first_call, n, *(_vp(a) for a in ins + outs), 0))
-        return tuple(outs)
+        return self._emit(self._L.ggrs_p2p_emit_spectator_packets, first_call, n, ack_in, resend, out, shapes)
 
     def read_spectator_emit_state(self):
         """(next_spectator_frame [S], last_acked [K][S], pending [K][S], status [K][S], closed_call

@@ -153,24 +153,9 @@ class SpectatorEngine:
         device, read in place by the launch."""
         n, S = int(start_frame.shape[0]), self.num_sessions
         stride = getattr(self, "packet_stride", None) or int(packets.shape[-1])
-        shapes = ((n, S), (n, S), (n, S, stride), (n, S))
-        dtypes = ("int32", "int32", "uint8", "int32")
         dev = hasattr(packets, "data_ptr") if on_device is None else bool(on_device)
-        keep, ptrs = [], []
-        for a, shape, dt in zip((start_frame, packet_len, packets, notes), shapes, dtypes):
-            if a is None:
-                ptrs.append(None)
-            elif dev:
-                if (not hasattr(a, "data_ptr") or tuple(a.shape) != shape or not a.is_contiguous()
-                        or str(a.dtype) != "torch." + dt or not a.is_cuda):
-                    raise InvalidRequest(-1, f"device arrays must be contiguous {dt} {shape} tensors on the device")
-                ptrs.append(ctypes.c_void_p(a.data_ptr()))
-            else:
-                a = np.ascontiguousarray(a, dt)
-                if a.shape != shape:
-                    raise InvalidRequest(-1, f"expected shape {shape}, got {a.shape}")
-                keep.append(a)
-                ptrs.append(_vp(a))
+        ptrs, keep = _lib.marshal((start_frame, packet_len, packets, notes), ((n, S), (n, S), (n, S, stride), (n, S)),
+                                  ("int32", "int32", "uint8", "int32"), dev)
         _lib.check(self._L.ggrs_spectator_receive_packets(self._h, first_call, n, *ptrs, int(dev)))
 
     def read_packet_results(self, first_call, n_calls):
