@@ -22,7 +22,7 @@ UNITS = ("engine.hip", "requests.hip", "branch.hip", "particles.hip", "p2p.hip",
 SOURCES = [os.path.join(CSRC, f) for f in UNITS]
 HEADERS = [os.path.join(CSRC, h) for h in ("box_game.h", "glibc_sincosf.h", "common.h", "particles.h", "p2p_engine.h",
                                            "engine.h", "host_device.h", "p2p_plan.h", "codec_device.h", "emit_device.h",
-                                           "ingest_device.h", "spectator_engine.h")] + [
+                                           "ingest_device.h", "p2p_device.h", "spectator_engine.h")] + [
     os.path.join(ROOT, "include", "ggrs_amd.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -31,6 +31,14 @@
 //   inputs   [C][S][Pp] u8    row g: local add_local_input of call g, remote inputs of frame g
 //   queue    [4][P][S]  i32   prediction.frame, prediction.input, first_incorrect, last_requested
 //   stats    rollbacks [S] i32, resim [S] i64
+//
+// The kernels here hold their forms' call logic.  What they share with each other and with the
+// scheduled kernels (p2p_sched.hip) -- a cell's packing, the ring copies between HBM and LDS, the
+// flat forms' row staging, the queue words, the desync-history store -- is in p2p_device.h; which
+// form a launch takes is p2p_plan.h's.  (p2p_kernel's row staging stays here: it is the dword form
+// of a 256-thread block, which the flat forms' 16-byte staging would not replace for free; so do
+// p2p_flat_kernel's queue words and the canonical kernels' desync-history store, which measured
+// slower through the helpers: profiles/p2p_shared_device_ab.json.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +47,7 @@
 #include <vector>
 
 #include "common.h"
+#include "p2p_device.h"
 #include "p2p_engine.h"
 #include "p2p_plan.h"
 
@@ -47,8 +56,6 @@
 using namespace ggrs;
 
 namespace {
-
-constexpr int32_t kNull = -1;  // NULL_FRAME (src/lib.rs:44)
 
 struct P2PParams {
   int64_t S;
@@ -74,53 +81,22 @@ struct P2PParams {
   int32_t* ring_frame;  // [R][S] frame each cell holds (sparse mode: saves vary per session)
 };
 
-constexpr int kHist = 32;  // MAX_CHECKSUM_HISTORY_SIZE (protocol.rs:27)
+// (kNull, kHist, RemoteQueues and the cell, ring, row-staging and queue helpers: p2p_device.h)
 
-// The per-session state of every remote player's InputQueue that the P2P program reads.
-template <int P>
-struct RemoteQueues {
-  int32_t pred_frame[P];  // prediction.frame (NULL: not predicting)
-  uint32_t pred_in[P];    // prediction.input
-  int32_t first_inc[P];   // first_incorrect_frame
-  int32_t last_req[P];    // last_requested_frame
-};
-
+// the HBM ring's cell of `slot` (session-major: piece stride 1)
 template <int P>
 __device__ inline uint4* ring_cell(const P2PParams& p, int32_t slot, int64_t sess) {
   return reinterpret_cast<uint4*>(p.ring + ((int64_t)sess * p.R + slot) * cell_dwords(P));
 }
+// the checksum stored with it (one dword read)
 template <int P>
-__device__ inline void load_cell(BoxState<P>& s, const uint4* c) {
-  constexpr int F = state_fields(P);
-#pragma unroll
-  for (int k = 0; k < cell_dwords(P) / 4; k++) {
-    const uint4 v = c[k];
-    const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-      if (4 * k + i < F) s.w[4 * k + i] = x[i];
-  }
-}
-template <int P>
-__device__ inline void store_cell(const BoxState<P>& s, uint32_t ck, uint4* c) {
-  constexpr int F = state_fields(P);
-#pragma unroll
-  for (int k = 0; k < cell_dwords(P) / 4; k++) {
-    uint32_t x[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) x[i] = 4 * k + i < F ? s.w[4 * k + i] : (4 * k + i == F ? ck : 0u);
-    c[k] = make_uint4(x[0], x[1], x[2], x[3]);
-  }
-}
-// the checksum stored with the cell of `slot`
-template <int P>
-__device__ inline uint16_t cell_checksum(const P2PParams& p, int32_t slot, int64_t sess) {
+__device__ inline uint16_t ring_cell_checksum(const P2PParams& p, int32_t slot, int64_t sess) {
   return (uint16_t)(p.ring + ((int64_t)sess * p.R + slot) * cell_dwords(P))[state_fields(P)];
 }
 
 template <int P>
 __device__ inline void save_cell(const P2PParams& p, const BoxState<P>& s, int32_t frame, int64_t sess) {
-  store_cell<P>(s, fletcher16_state<P>(s), ring_cell<P>(p, frame % p.R, sess));
+  cell_pack<P, 1>(s, fletcher16_state<P>(s), ring_cell<P>(p, frame % p.R, sess));
 }
 
 // Input rows as the calls read them: from global memory, or (staged kernel) from the block's LDS
@@ -200,13 +176,7 @@ __global__ __launch_bounds__(kP2PBlock) void p2p_kernel(P2PParams p) {
   BoxState<P> st;
   load_state<P>(st, p.cur + sess, S);
   RemoteQueues<P> q;
-#pragma unroll
-  for (int k = 0; k < P; k++) {
-    q.pred_frame[k] = p.queue[(0 * P + k) * S + sess];
-    q.pred_in[k] = (uint32_t)p.queue[(1 * P + k) * S + sess];
-    q.first_inc[k] = p.queue[(2 * P + k) * S + sess];
-    q.last_req[k] = p.queue[(3 * P + k) * S + sess];
-  }
+  load_queues<P>(q, p.queue, S, sess);
   int32_t rollbacks = 0;
   int64_t resim = 0;
   const bool dbg = live && sess == p.dbg_sess;
@@ -259,22 +229,16 @@ __global__ __launch_bounds__(kP2PBlock) void p2p_kernel(P2PParams p) {
   int32_t pre_frame = kNull;
   auto prefetch = [&](int32_t fr) {
     if (!p.sparse && fr >= 0) {
-      load_cell<P>(pre, ring_cell<P>(p, fr % p.R, sess));
+      cell_unpack<P, 1>(pre, ring_cell<P>(p, fr % p.R, sess));
       pre_frame = fr;
     }
   };
   prefetch(p.f0 - p.D);
   lean_ok = lean_ok && __all(pre_frame == kNull || rot_in_domain<P>(pre));
   auto call = [&](int32_t f, const auto& input_row) {
-    // 0. check_checksum_send_interval (p2p_session.rs:939-975), before any rollback of this call:
-    //    last_confirmed_frame = f - 1 - D and last_saved_frame = f - 1 here, so frame_to_send =
-    //    interval, 2 interval, ... goes out at call frame_to_send + D + 1; its cell is in the ring
-    //    (D + 1 < R), its checksum enters the local history
-    if (p.desync_interval > 0 && live) {
-      const int32_t fts = f - 1 - p.D;
-      if (fts >= p.desync_interval && fts % p.desync_interval == 0)
-        p.hist[(int64_t)((fts / p.desync_interval) % kHist) * S + sess] = cell_checksum<P>(p, fts % p.R, sess);
-    }
+    // 0. check_checksum_send_interval, before any rollback of this call
+    store_desync_history(p.hist, p.desync_interval, f, p.D, p.R, S, sess, live,
+                         [&](int32_t slot) { return ring_cell_checksum<P>(p, slot, sess); });
     // 1. poll_remote_clients: the remote input of frame g = f - D (add_input_by_frame)
     const int32_t g = f - p.D;
     const int32_t last_added = g >= 0 ? g : kNull;
@@ -300,7 +264,7 @@ __global__ __launch_bounds__(kP2PBlock) void p2p_kernel(P2PParams p) {
     auto adjust = [&](int32_t first_incorrect) {
       const int32_t load = p.sparse ? last_saved : first_incorrect;  // sparse: the last save
       if (load == pre_frame) st = pre;
-      else load_cell<P>(st, ring_cell<P>(p, load % p.R, sess));
+      else cell_unpack<P, 1>(st, ring_cell<P>(p, load % p.R, sess));
 #pragma unroll
       for (int k = 0; k < P; k++) {  // reset_prediction (input_queue.rs:63-67)
         q.pred_frame[k] = kNull;
@@ -348,13 +312,7 @@ __global__ __launch_bounds__(kP2PBlock) void p2p_kernel(P2PParams p) {
   }
   if (!live) return;
   store_state<P>(st, p.cur + sess, S);
-#pragma unroll
-  for (int k = 0; k < P; k++) {
-    p.queue[(0 * P + k) * S + sess] = q.pred_frame[k];
-    p.queue[(1 * P + k) * S + sess] = (int32_t)q.pred_in[k];
-    p.queue[(2 * P + k) * S + sess] = q.first_inc[k];
-    p.queue[(3 * P + k) * S + sess] = q.last_req[k];
-  }
+  store_queues<P>(q, p.queue, S, sess);
   p.rollbacks[sess] += rollbacks;
   p.resim[sess] += resim;
   if (p.sparse) p.last_saved[sess] = last_saved;
@@ -445,6 +403,9 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_flat_kernel(P2PParams p) {
   BoxState<P> st;
   load_state<P>(st, p.cur + sess, S);
   RemoteQueues<P> q;
+  // (The queue words are written out in this kernel, here and at its end, not p2p_device.h's
+  // load_queues / store_queues: through the helpers the HBM-ring form's launch measured 0.2-0.5 %
+  // longer, past the parent's own spread, in three jobs; written out it is within it.)
 #pragma unroll
   for (int k = 0; k < P; k++) {
     q.pred_frame[k] = p.queue[(0 * P + k) * S + sess];
@@ -462,58 +423,25 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_flat_kernel(P2PParams p) {
   // last save (sparse)
   uint4* const my_ring = reinterpret_cast<uint4*>(p.ring + (int64_t)sess * p.R * cell_dwords(P));
   auto cell = [&](int32_t slot) { return my_ring + slot * (cell_dwords(P) / 4); };
-  auto next_slot = [&](int32_t x) { return x + 1 == p.R ? 0 : x + 1; };
   // the ring cell of `slot`: HBM (session-major) or this lane's LDS column (piece stride 64)
   const int lt = threadIdx.x;  // LDS column: idle threads keep their own, unused one
   auto cell_load = [&](BoxState<P>& dst, int32_t slot) {
-    if constexpr (kLds) {
-      constexpr int F = state_fields(P);
-#pragma unroll
-      for (int k = 0; k < PC; k++) {
-        const uint4 v = lds_ring[(slot * PC + k) * kFlatBlock + lt];
-        const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-          if (4 * k + i < F) dst.w[4 * k + i] = x[i];
-      }
-    } else {
-      load_cell<P>(dst, cell(slot));
-    }
+    if constexpr (kLds) cell_unpack<P, kFlatBlock>(dst, lds_ring + slot * PC * kFlatBlock + lt);
+    else cell_unpack<P, 1>(dst, cell(slot));
   };
   auto cell_store = [&](const BoxState<P>& src, uint32_t ck, int32_t slot) {
-    if constexpr (kLds) {
-      constexpr int F = state_fields(P);
-#pragma unroll
-      for (int k = 0; k < PC; k++) {
-        uint32_t x[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) x[i] = 4 * k + i < F ? src.w[4 * k + i] : (4 * k + i == F ? ck : 0u);
-        lds_ring[(slot * PC + k) * kFlatBlock + lt] = make_uint4(x[0], x[1], x[2], x[3]);
-      }
-    } else {
-      store_cell<P>(src, ck, cell(slot));
-    }
+    if constexpr (kLds) cell_pack<P, kFlatBlock>(src, ck, lds_ring + slot * PC * kFlatBlock + lt);
+    else cell_pack<P, 1>(src, ck, cell(slot));
   };
   auto cell_ck = [&](int32_t slot) -> uint16_t {
-    if constexpr (kLds) {
-      constexpr int F = state_fields(P);
-      const uint4 v = lds_ring[(slot * PC + F / 4) * kFlatBlock + lt];
-      const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-      return (uint16_t)x[F % 4];
-    } else {
-      return cell_checksum<P>(p, slot, sess);
-    }
+    if constexpr (kLds) return cell_checksum<P, kFlatBlock>(lds_ring + slot * PC * kFlatBlock + lt);
+    else return ring_cell_checksum<P>(p, slot, sess);
   };
-  // kLds: the block's rings into LDS (HBM pieces are contiguous per block: coalesced reads)
+  // kLds: the block's rings into LDS
   const int ring_pieces = p.R * PC;
+  uint4* const gring = reinterpret_cast<uint4*>(p.ring) + sess0 * ring_pieces;
   if constexpr (kLds) {
-    const int n = nb * ring_pieces;
-    const uint4* src = reinterpret_cast<const uint4*>(p.ring) + sess0 * ring_pieces;
-#pragma unroll 4
-    for (int i = lt; i < n; i += kFlatBlock) {
-      const int sl = i / ring_pieces, rem = i - sl * ring_pieces;
-      lds_ring[rem * kFlatBlock + sl] = src[i];
-    }
+    ring_to_lds<kFlatBlock, kFlatBlock, 4>(lds_ring, gring, nb, ring_pieces);
     __syncthreads();
   }
   int32_t slot_f = p.f0 % p.R, slot_h = 0, pre_slot = 0;
@@ -537,43 +465,20 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_flat_kernel(P2PParams p) {
   // prefetch(fr, slot): fr = f + 1 - D with 1 <= D < R, so its slot is slot_f + 1 - D mod R
   auto prefetch = [&](int32_t fr, int32_t slot) {
     if (!kSparse && !kLds && fr >= 0) {  // (an LDS cell is read where the rollback happens)
-      load_cell<P>(pre, cell(slot));
+      cell_unpack<P, 1>(pre, cell(slot));
       pre_frame = fr;
       pre_slot = slot;
     }
   };
-  {
-    const int32_t s0 = slot_f - p.D;
-    prefetch(p.f0 - p.D, s0 < 0 ? s0 + p.R : s0);
-  }
+  prefetch(p.f0 - p.D, back_slot(slot_f, p.D, p.R));
   // every state this launch steps descends from cur or from a ring cell, all written by this
   // engine (or zero-initialised) and so inside the lean step's rotation domain; one wave-wide test
   // here instead of one per player per step (a foreign state takes the general step throughout)
   const bool lean_ok = __all(rot_in_domain<P>(st) && (pre_frame == kNull || rot_in_domain<P>(pre)));
   const int32_t f_end = p.f0 + p.n;
-  const int32_t calls_per_stage = kRows - back;  // >= 1 (host)
   for (int32_t fs = p.f0; fs < f_end;) {
-    const int32_t chunk_end = min(f_end, fs + calls_per_stage);
-    const int32_t lo = max(0, fs - back);
-    {  // stage rows [lo, chunk_end)
-      __syncthreads();
-      const int nrows = chunk_end - lo, row_bytes = nb * Pp;
-      if (nb == kFlatBlock && ((S * Pp) & 15) == 0) {  // whole 16-byte pieces, every load in flight
-        constexpr int kPieces = kFlatBlock * Pp / 16;
-#pragma unroll 4
-        for (int c = threadIdx.x; c < nrows * kPieces; c += kFlatBlock) {
-          const int r = c / kPieces, k = c - r * kPieces;
-          const uint4* src = reinterpret_cast<const uint4*>(p.inputs + ((int64_t)((lo + r) % p.cap) * S + sess0) * Pp);
-          reinterpret_cast<uint4*>(lds_rows + r * kFlatBlock * Pp)[k] = src[k];
-        }
-      } else {
-        for (int c = threadIdx.x; c < nrows * row_bytes; c += kFlatBlock) {
-          const int r = c / row_bytes, b = c - r * row_bytes;
-          lds_rows[r * kFlatBlock * Pp + b] = p.inputs[((int64_t)((lo + r) % p.cap) * S + sess0) * Pp + b];
-        }
-      }
-      __syncthreads();
-    }
+    const RowStage sg = stage_rows<Pp, kFlatBlock, kRows>(lds_rows, p.inputs, S, p.cap, sess0, nb, lt, fs, f_end, back);
+    const int32_t chunk_end = sg.end, lo = sg.lo;
     const LdsRowsFlat<P> rows{lds_rows, lo, tid};
     int32_t f = fs;              // this session's call
     bool at_start = true, replaying = false, window_done = false;
@@ -590,8 +495,7 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_flat_kernel(P2PParams p) {
       } else {
         // load >= f - max_prediction (the remote input of frame f - D arrives at call f, D <
         // max_prediction), so its slot is slot_f - (f - load) with at most one wrap
-        const int32_t sh = slot_f - (f - load);
-        slot_h = sh < 0 ? sh + p.R : sh;
+        slot_h = back_slot(slot_f, f - load, p.R);
         cell_load(st, slot_h);
       }
 #pragma unroll
@@ -616,11 +520,7 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_flat_kernel(P2PParams p) {
     while (f < chunk_end) {
       if (at_start) {
         // 0. check_checksum_send_interval (as p2p_kernel)
-        if (!kPlain && p.desync_interval > 0 && live) {
-          const int32_t fts = f - 1 - p.D;
-          if (fts >= p.desync_interval && fts % p.desync_interval == 0)
-            p.hist[(int64_t)((fts / p.desync_interval) % kHist) * S + sess] = cell_ck(fts % p.R);
-        }
+        if (!kPlain) store_desync_history(p.hist, p.desync_interval, f, p.D, p.R, S, sess, live, cell_ck);
         // 1. poll_remote_clients: the remote input of frame g = f - D (add_input_by_frame)
         const int32_t g = f - p.D;
         last_added = g >= 0 ? g : kNull;
@@ -668,23 +568,22 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_flat_kernel(P2PParams p) {
       if (dbg && (int32_t)from == p.dbg_frame) st.w[fld_x(P, 0)] ^= 1u;
       if constexpr (kPlain && kLds && !kSparse) {  // the same bookkeeping as selects
         const bool rep = replaying;
-        slot_h = rep ? next_slot(slot_h) : slot_h;
+        slot_h = rep ? next_slot(slot_h, p.R) : slot_h;
         h = rep ? h + 1 : h;
         replaying = rep && h != f;
-        slot_f = rep ? slot_f : next_slot(slot_f);
+        slot_f = rep ? slot_f : next_slot(slot_f, p.R);
         f = rep ? f : f + 1;
         at_start = !rep;
       } else if (replaying) {
-        slot_h = next_slot(slot_h);
+        slot_h = next_slot(slot_h, p.R);
         if (++h == f) {
           replaying = false;
           if (kSparse && !window_done) window_check();  // may replay again from the last save
         }
       } else {
         if (!kPlain && p.trace && live) p.trace[(int64_t)(f % p.trace_cap) * S + sess] = fletcher16_state<P>(st);
-        const int32_t ps = slot_f + 1 - p.D;
-        prefetch(f + 1 - p.D, ps < 0 ? ps + p.R : ps);
-        slot_f = next_slot(slot_f);
+        prefetch(f + 1 - p.D, back_slot(slot_f + 1, p.D, p.R));
+        slot_f = next_slot(slot_f, p.R);
         ++f;
         at_start = true;
       }
@@ -693,12 +592,7 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_flat_kernel(P2PParams p) {
   }
   if constexpr (kLds) {  // the rings back to HBM
     __syncthreads();
-    const int n = nb * ring_pieces;
-    uint4* dst = reinterpret_cast<uint4*>(p.ring) + sess0 * ring_pieces;
-    for (int i = lt; i < n; i += kFlatBlock) {
-      const int sl = i / ring_pieces, rem = i - sl * ring_pieces;
-      dst[i] = lds_ring[rem * kFlatBlock + sl];
-    }
+    ring_from_lds<kFlatBlock, kFlatBlock>(gring, lds_ring, nb, ring_pieces);
   }
   if (!live) return;
   store_state<P>(st, p.cur + sess, S);
@@ -735,7 +629,6 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_kernel(P2PParams p) {
   constexpr int Pp = P <= 1 ? 1 : (P == 2 ? 2 : 4);
   constexpr int kRows = flat_rows_lds<P>();
   constexpr int PC = cell_dwords(P) / 4;
-  constexpr int F = state_fields(P);
   __shared__ __attribute__((aligned(16))) uint8_t lds_rows[kRows * kFlatBlock * Pp];
   extern __shared__ uint4 lds_ring[];  // [R][PC][kFlatBlock]
   const int64_t sess0 = (int64_t)blockIdx.x * kFlatBlock;
@@ -745,11 +638,8 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_kernel(P2PParams p) {
   const int nb = (int)((S - sess0) < kFlatBlock ? (S - sess0) : kFlatBlock);
   const int lt = threadIdx.x;
   const int tid = live ? lt : 0;
-  // byte masks of the local and remote players' inputs in a packed row
-  uint32_t lbytes = 0;
-#pragma unroll
-  for (int k = 0; k < P; k++) lbytes |= ((lmask >> k) & 1u) ? 0xffu << (8 * k) : 0u;
-  const uint32_t rbytes = (P == 4 ? 0xffffffffu : ((1u << (8 * P)) - 1u)) & ~lbytes;
+  const ByteMasks bm = input_byte_masks<P>(lmask);
+  const uint32_t lbytes = bm.lbytes, rbytes = bm.rbytes;
   BoxState<P> st;
   load_state<P>(st, p.cur + sess, S);
   // the prediction in effect before the launch: the remote inputs of frame f0 - 1 - D (canonical
@@ -784,55 +674,19 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_kernel(P2PParams p) {
     }
   }
   __syncthreads();
-  auto cell_load = [&](int32_t slot) {
-#pragma unroll
-    for (int k = 0; k < PC; k++) {
-      const uint4 v = lds_ring[(slot * PC + k) * kFlatBlock + lt];
-      const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-        if (4 * k + i < F) st.w[4 * k + i] = x[i];
-    }
-  };
+  // this lane's LDS cell of `slot`
+  auto cell_load = [&](int32_t slot) { cell_unpack<P, kFlatBlock>(st, lds_ring + slot * PC * kFlatBlock + lt); };
   auto cell_store = [&](int32_t slot) {
-    const uint32_t ck = fletcher16_state<P>(st);
-#pragma unroll
-    for (int k = 0; k < PC; k++) {
-      uint32_t x[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) x[i] = 4 * k + i < F ? st.w[4 * k + i] : (4 * k + i == F ? ck : 0u);
-      lds_ring[(slot * PC + k) * kFlatBlock + lt] = make_uint4(x[0], x[1], x[2], x[3]);
-    }
+    cell_pack<P, kFlatBlock>(st, fletcher16_state<P>(st), lds_ring + slot * PC * kFlatBlock + lt);
   };
-  auto next_slot = [&](int32_t x) { return x + 1 == p.R ? 0 : x + 1; };
   const bool lean_ok = __all(rot_in_domain<P>(st));
   int32_t rollbacks = 0;
   int32_t slot_f = p.f0 % p.R, slot_h = 0;
   const int32_t f_end = p.f0 + p.n;
   const int32_t back = p.D + p.delay;
-  const int32_t calls_per_stage = kRows - back;  // >= 1 (host)
   for (int32_t fs = p.f0; fs < f_end;) {
-    const int32_t chunk_end = min(f_end, fs + calls_per_stage);
-    const int32_t lo = max(0, fs - back);
-    {
-      __syncthreads();
-      const int nrows = chunk_end - lo, row_bytes = nb * Pp;
-      if (nb == kFlatBlock && ((S * Pp) & 15) == 0) {
-        constexpr int kPieces = kFlatBlock * Pp / 16;
-#pragma unroll 4
-        for (int c = lt; c < nrows * kPieces; c += kFlatBlock) {
-          const int r = c / kPieces, k = c - r * kPieces;
-          const uint4* src = reinterpret_cast<const uint4*>(p.inputs + ((int64_t)((lo + r) % p.cap) * S + sess0) * Pp);
-          reinterpret_cast<uint4*>(lds_rows + r * kFlatBlock * Pp)[k] = src[k];
-        }
-      } else {
-        for (int c = lt; c < nrows * row_bytes; c += kFlatBlock) {
-          const int r = c / row_bytes, b = c - r * row_bytes;
-          lds_rows[r * kFlatBlock * Pp + b] = p.inputs[((int64_t)((lo + r) % p.cap) * S + sess0) * Pp + b];
-        }
-      }
-      __syncthreads();
-    }
+    const RowStage sg = stage_rows<Pp, kFlatBlock, kRows>(lds_rows, p.inputs, S, p.cap, sess0, nb, lt, fs, f_end, back);
+    const int32_t chunk_end = sg.end, lo = sg.lo;
     const LdsRowsFlat<P> rows{lds_rows, lo, tid};
     int32_t f = fs, h = 0, g = 0;
     bool at_start = true, replaying = false;
@@ -841,15 +695,14 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_kernel(P2PParams p) {
     uint32_t next_rem = rows(fs - p.D) & rbytes;
     while (f < chunk_end) {
       if (at_start) {
-        // check_checksum_send_interval (p2p_session.rs:939-975), before any rollback of this call
-        // (as p2p_kernel); a launch-uniform switch
+        // check_checksum_send_interval (p2p_session.rs:939-975), before any rollback of this call; a
+        // launch-uniform switch.  (The store is written out here, not p2p_device.h's
+        // store_desync_history: through it this kernel's launch measured 6 % longer with detection off.)
         if (p.desync_interval > 0) {
           const int32_t fts = f - 1 - p.D;
           if (live && fts >= p.desync_interval && fts % p.desync_interval == 0) {
-            const int32_t cs = fts % p.R;
-            const uint4 v = lds_ring[(cs * PC + F / 4) * kFlatBlock + lt];
-            const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-            p.hist[(int64_t)((fts / p.desync_interval) % kHist) * S + sess] = (uint16_t)x[F % 4];
+            p.hist[(int64_t)((fts / p.desync_interval) % kHist) * S + sess] =
+                cell_checksum<P, kFlatBlock>(lds_ring + (fts % p.R) * PC * kFlatBlock + lt);
           }
         }
         // poll of call f: the remote inputs of frame g = f - D against the prediction made for them
@@ -860,8 +713,7 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_kernel(P2PParams p) {
         prev_rem = rem_conf;
         rem_pred = p.predictor == 0 ? rem_conf : 0u;
         if (miss) {  // adjust_gamestate: LoadGameState(g), replay g .. f - 1
-          const int32_t sh = slot_f - p.D;
-          slot_h = sh < 0 ? sh + p.R : sh;
+          slot_h = back_slot(slot_f, p.D, p.R);
           cell_load(slot_h);
           h = g;
           replaying = true;
@@ -876,10 +728,10 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_kernel(P2PParams p) {
       if (lean_ok) advance_state_lean<P>(st, local | rem);
       else advance_state<P>(st, local | rem, 0u);
       const bool rep = replaying;
-      slot_h = rep ? next_slot(slot_h) : slot_h;
+      slot_h = rep ? next_slot(slot_h, p.R) : slot_h;
       h = rep ? h + 1 : h;
       replaying = rep && h != f;
-      slot_f = rep ? slot_f : next_slot(slot_f);
+      slot_f = rep ? slot_f : next_slot(slot_f, p.R);
       f = rep ? f : f + 1;
       at_start = !rep;
     }
@@ -904,15 +756,7 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_kernel(P2PParams p) {
   }
   if (!live) return;
   store_state<P>(st, p.cur + sess, S);
-  const int32_t t_last = f_end - 1;
-#pragma unroll
-  for (int k = 0; k < P; k++) {
-    if ((lmask >> k) & 1u) continue;
-    p.queue[(0 * P + k) * S + sess] = t_last - p.D + 1;
-    p.queue[(1 * P + k) * S + sess] = (int32_t)(p.predictor == 0 ? (prev_rem >> (8 * k)) & 0xffu : 0u);
-    p.queue[(2 * P + k) * S + sess] = kNull;
-    p.queue[(3 * P + k) * S + sess] = t_last;
-  }
+  store_canonical_queues<P>(p.queue, S, sess, lmask, f_end - 1, p.D, p.predictor, prev_rem);
   p.rollbacks[sess] += rollbacks;
   p.resim[sess] += (int64_t)rollbacks * p.D;
 }
@@ -933,7 +777,6 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_sparse_kernel(P2PParams 
   constexpr int Pp = P <= 1 ? 1 : (P == 2 ? 2 : 4);
   constexpr int kRows = flat_rows_lds<P>();
   constexpr int PC = cell_dwords(P) / 4;
-  constexpr int F = state_fields(P);
   __shared__ __attribute__((aligned(16))) uint8_t lds_rows[kRows * kFlatBlock * Pp];
   extern __shared__ uint4 lds_ring[];  // [R][PC][kFlatBlock]
   const int64_t sess0 = (int64_t)blockIdx.x * kFlatBlock;
@@ -943,10 +786,8 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_sparse_kernel(P2PParams 
   const int nb = (int)((S - sess0) < kFlatBlock ? (S - sess0) : kFlatBlock);
   const int lt = threadIdx.x;
   const int tid = live ? lt : 0;
-  uint32_t lbytes = 0;
-#pragma unroll
-  for (int k = 0; k < P; k++) lbytes |= ((lmask >> k) & 1u) ? 0xffu << (8 * k) : 0u;
-  const uint32_t rbytes = (P == 4 ? 0xffffffffu : ((1u << (8 * P)) - 1u)) & ~lbytes;
+  const ByteMasks bm = input_byte_masks<P>(lmask);
+  const uint32_t lbytes = bm.lbytes, rbytes = bm.rbytes;
   BoxState<P> st;
   load_state<P>(st, p.cur + sess, S);
   uint32_t prev_rem = 0;
@@ -956,69 +797,25 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_sparse_kernel(P2PParams 
   int32_t last_saved = p.last_saved[sess];
   int32_t saved_slot = last_saved >= 0 ? last_saved % p.R : 0;
   const int ring_pieces = p.R * PC;
-  {
-    const int n = nb * ring_pieces;
-    const uint4* src = reinterpret_cast<const uint4*>(p.ring) + sess0 * ring_pieces;
-#pragma unroll 4
-    for (int i = lt; i < n; i += kFlatBlock) {
-      const int sl = i / ring_pieces, rem = i - sl * ring_pieces;
-      lds_ring[rem * kFlatBlock + sl] = src[i];
-    }
-  }
+  uint4* const gring = reinterpret_cast<uint4*>(p.ring) + sess0 * ring_pieces;
+  ring_to_lds<kFlatBlock, kFlatBlock, 4>(lds_ring, gring, nb, ring_pieces);
   __syncthreads();
-  auto cell_load = [&](int32_t slot) {
-#pragma unroll
-    for (int k = 0; k < PC; k++) {
-      const uint4 v = lds_ring[(slot * PC + k) * kFlatBlock + lt];
-      const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-        if (4 * k + i < F) st.w[4 * k + i] = x[i];
-    }
-  };
+  auto cell_load = [&](int32_t slot) { cell_unpack<P, kFlatBlock>(st, lds_ring + slot * PC * kFlatBlock + lt); };
   auto save = [&](int32_t h, int32_t slot) {  // SaveGameState(h): the cell and its frame tag
-    const uint32_t ck = fletcher16_state<P>(st);
-#pragma unroll
-    for (int k = 0; k < PC; k++) {
-      uint32_t x[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) x[i] = 4 * k + i < F ? st.w[4 * k + i] : (4 * k + i == F ? ck : 0u);
-      lds_ring[(slot * PC + k) * kFlatBlock + lt] = make_uint4(x[0], x[1], x[2], x[3]);
-    }
+    cell_pack<P, kFlatBlock>(st, fletcher16_state<P>(st), lds_ring + slot * PC * kFlatBlock + lt);
     if (live) p.ring_frame[(int64_t)slot * S + sess] = h;
     last_saved = h;
     saved_slot = slot;
   };
-  auto next_slot = [&](int32_t x) { return x + 1 == p.R ? 0 : x + 1; };
   const bool lean_ok = __all(rot_in_domain<P>(st));
   int32_t rollbacks = 0;
   int64_t resim = 0;
   int32_t slot_f = p.f0 % p.R, slot_h = 0;
   const int32_t f_end = p.f0 + p.n;
   const int32_t back = p.R - 1 + p.delay;       // a replay reaches back to the last save
-  const int32_t calls_per_stage = kRows - back;  // >= 1 (host)
   for (int32_t fs = p.f0; fs < f_end;) {
-    const int32_t chunk_end = min(f_end, fs + calls_per_stage);
-    const int32_t lo = max(0, fs - back);
-    {
-      __syncthreads();
-      const int nrows = chunk_end - lo, row_bytes = nb * Pp;
-      if (nb == kFlatBlock && ((S * Pp) & 15) == 0) {
-        constexpr int kPieces = kFlatBlock * Pp / 16;
-#pragma unroll 4
-        for (int c = lt; c < nrows * kPieces; c += kFlatBlock) {
-          const int r = c / kPieces, k = c - r * kPieces;
-          const uint4* src = reinterpret_cast<const uint4*>(p.inputs + ((int64_t)((lo + r) % p.cap) * S + sess0) * Pp);
-          reinterpret_cast<uint4*>(lds_rows + r * kFlatBlock * Pp)[k] = src[k];
-        }
-      } else {
-        for (int c = lt; c < nrows * row_bytes; c += kFlatBlock) {
-          const int r = c / row_bytes, b = c - r * row_bytes;
-          lds_rows[r * kFlatBlock * Pp + b] = p.inputs[((int64_t)((lo + r) % p.cap) * S + sess0) * Pp + b];
-        }
-      }
-      __syncthreads();
-    }
+    const RowStage sg = stage_rows<Pp, kFlatBlock, kRows>(lds_rows, p.inputs, S, p.cap, sess0, nb, lt, fs, f_end, back);
+    const int32_t chunk_end = sg.end, lo = sg.lo;
     const LdsRowsFlat<P> rows{lds_rows, lo, tid};
     int32_t f = fs, h = 0, g = 0;
     bool at_start = true, replaying = false, window_done = false;
@@ -1040,13 +837,14 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_sparse_kernel(P2PParams 
     };
     while (f < chunk_end) {
       if (at_start) {
-        if (p.desync_interval > 0) {  // check_checksum_send_interval (as the canonical kernel)
+        // check_checksum_send_interval (p2p_session.rs:939-975), before any rollback of this call; a
+        // launch-uniform switch.  (The store is written out here, not p2p_device.h's
+        // store_desync_history: through it this kernel's launch measured 6 % longer with detection off.)
+        if (p.desync_interval > 0) {
           const int32_t fts = f - 1 - p.D;
           if (live && fts >= p.desync_interval && fts % p.desync_interval == 0) {
-            const int32_t cs = fts % p.R;
-            const uint4 v = lds_ring[(cs * PC + F / 4) * kFlatBlock + lt];
-            const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-            p.hist[(int64_t)((fts / p.desync_interval) % kHist) * S + sess] = (uint16_t)x[F % 4];
+            p.hist[(int64_t)((fts / p.desync_interval) % kHist) * S + sess] =
+                cell_checksum<P, kFlatBlock>(lds_ring + (fts % p.R) * PC * kFlatBlock + lt);
           }
         }
         g = f - p.D;
@@ -1067,13 +865,13 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_sparse_kernel(P2PParams 
       if (lean_ok) advance_state_lean<P>(st, local | rem);
       else advance_state<P>(st, local | rem, 0u);
       if (replaying) {
-        slot_h = next_slot(slot_h);
+        slot_h = next_slot(slot_h, p.R);
         if (++h == f) {
           replaying = false;
           if (!window_done) window_check();  // may replay again from the last save
         }
       } else {
-        slot_f = next_slot(slot_f);
+        slot_f = next_slot(slot_f, p.R);
         ++f;
         at_start = true;
       }
@@ -1081,25 +879,10 @@ __global__ __launch_bounds__(kFlatBlock) void p2p_canon_sparse_kernel(P2PParams 
     fs = chunk_end;
   }
   __syncthreads();
-  {
-    const int n = nb * ring_pieces;
-    uint4* dst = reinterpret_cast<uint4*>(p.ring) + sess0 * ring_pieces;
-    for (int i = lt; i < n; i += kFlatBlock) {
-      const int sl = i / ring_pieces, rem = i - sl * ring_pieces;
-      dst[i] = lds_ring[rem * kFlatBlock + sl];
-    }
-  }
+  ring_from_lds<kFlatBlock, kFlatBlock>(gring, lds_ring, nb, ring_pieces);
   if (!live) return;
   store_state<P>(st, p.cur + sess, S);
-  const int32_t t_last = f_end - 1;
-#pragma unroll
-  for (int k = 0; k < P; k++) {
-    if ((lmask >> k) & 1u) continue;
-    p.queue[(0 * P + k) * S + sess] = t_last - p.D + 1;
-    p.queue[(1 * P + k) * S + sess] = (int32_t)(p.predictor == 0 ? (prev_rem >> (8 * k)) & 0xffu : 0u);
-    p.queue[(2 * P + k) * S + sess] = kNull;
-    p.queue[(3 * P + k) * S + sess] = t_last;
-  }
+  store_canonical_queues<P>(p.queue, S, sess, lmask, f_end - 1, p.D, p.predictor, prev_rem);
   p.rollbacks[sess] += rollbacks;
   p.resim[sess] += resim;
   p.last_saved[sess] = last_saved;
@@ -1557,10 +1340,7 @@ __global__ __launch_bounds__(256) void p2p_lockstep_kernel(P2PParams p, const in
   const int64_t S = p.S;
   BoxState<P> st;
   load_state<P>(st, p.cur + sess, S);
-  uint32_t lbytes = 0;  // the local players' bytes of the packed input word
-#pragma unroll
-  for (int k = 0; k < P; k++)
-    if ((p.local_mask >> k) & 1u) lbytes |= 0xffu << (8 * k);
+  const uint32_t lbytes = input_byte_masks<P>(p.local_mask).lbytes;  // the local players' bytes of the packed input word
   for (int32_t k = 0; k < p.n; k++) {
     const int32_t lrow = prog[2 * k], rrow = prog[2 * k + 1];
     if (rrow >= 0) {  // AdvanceFrame with synchronized_inputs (all confirmed)
@@ -1588,12 +1368,11 @@ __global__ __launch_bounds__(256) void compare_checksums_kernel(const uint16_t* 
 }
 
 // every queue starts empty: prediction.frame, first_incorrect, last_requested = NULL, input 0
-__global__ void init_queue_kernel(int32_t* queue, int64_t n_per_field, int32_t P) {
+__global__ void init_queue_kernel(int32_t* queue, int64_t n_per_field) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 4 * n_per_field) return;
   const int64_t field = i / n_per_field;
   queue[i] = field == 1 ? 0 : kNull;
-  (void)P;
 }
 
 }  // namespace
@@ -1817,7 +1596,7 @@ int ggrs_p2p_engine_create(const ggrs_p2p_config_t* cfg, ggrs_p2p_engine_t** out
   CTRY(hipMemsetAsync(e->rollbacks, 0, sizeof(int32_t) * S, e->stream));
   CTRY(hipMemsetAsync(e->resim, 0, sizeof(int64_t) * S, e->stream));
   if (e->trace) CTRY(hipMemsetAsync(e->trace, 0, sizeof(uint16_t) * (size_t)c.trace_capacity * S, e->stream));
-  init_queue_kernel<<<grid_of(4 * P * S, 256), 256, 0, e->stream>>>(e->queue, (int64_t)P * S, P);
+  init_queue_kernel<<<grid_of(4 * P * S, 256), 256, 0, e->stream>>>(e->queue, (int64_t)P * S);
   dispatch_players(P, [&](auto PC) {
     constexpr int PP = decltype(PC)::value;
     init_states_kernel<PP><<<grid_of(S, 256), 256, 0, e->stream>>>(e->cur, S);

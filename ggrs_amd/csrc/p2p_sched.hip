@@ -29,6 +29,9 @@
 //                           skipped calls, the session's error, the disconnected mask, and per
 //                           player last_frame (local_connect_status); the remote InputQueues'
 //                           prediction state is implied (the canonical form, in the kernel)
+//
+// A cell's packing, the ring copies between HBM and LDS, the byte masks and the slot arithmetic are
+// p2p_device.h's, shared with p2p.hip's kernels; the launch plan is p2p_plan.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +41,7 @@
 #include <vector>
 
 #include "common.h"
+#include "p2p_device.h"
 #include "p2p_engine.h"
 #include "p2p_plan.h"
 
@@ -47,7 +51,6 @@ using namespace ggrs;
 
 namespace {
 
-constexpr int32_t kNull = GGRS_NULL_FRAME;
 constexpr int kQ = 128;  // INPUT_QUEUE_LENGTH (input_queue.rs:6)
 
 enum : int { kCur = 0, kLconf, kDframe, kLastSaved, kDelivered, kLocalLast, kSkips, kErr, kDisc, kLastSent, kRmask, kLastCk, kPl0 };
@@ -57,7 +60,6 @@ constexpr int kPlFields = 1;  // per player: last_frame (local_connect_status; r
 __host__ __device__ constexpr int sched_rep0(int P) { return kPl0 + kPlFields * P; }
 __host__ __device__ constexpr int sched_fields(int P) { return sched_rep0(P) + P * P; }
 constexpr uint32_t kEvPeerReport = 0x10u;  // an events byte's flag: the call carries a peer report
-__host__ __device__ constexpr int cell_dwords_s(int p) { return cell_dwords(p); }
 
 struct SchedParams {
   int64_t S;
@@ -212,7 +214,7 @@ __device__ __forceinline__ bool sched_fast_call(SchedCtl<P>& q, const SchedCtlEn
   // the prediction threshold (:393-423): frames_ahead is current_frame while nothing is confirmed
   // (PredictDefault lets a session with nothing delivered take this form)
   const bool adv = (lc == kNull ? q.cur : q.cur - lc) < maxp;
-  const int32_t nslot = q.slot_f + 1 == x.R ? 0 : q.slot_f + 1;
+  const int32_t nslot = next_slot(q.slot_f, x.R);
   if (fast) {
     rep = send ? fts : kNull;
     q.last_sent = send ? fts : q.last_sent;
@@ -245,8 +247,6 @@ __device__ __forceinline__ uint2 sched_control_call(SchedCtl<P>& q, const SchedC
   using T = typename InputWord<P>::T;
   const int32_t lo = x.lo, maxp = x.maxp, R = x.R;
   const uint32_t lmask = x.lmask, lbytes = x.lbytes, rbytes = x.rbytes;
-  auto next_slot = [&](int32_t v) { return v + 1 == R ? 0 : v + 1; };
-  auto back_slot = [&](int32_t v, int32_t d) { const int32_t y = v - d; return y < 0 ? y + R : y; };
   // a row's frame tag: staged, or (older than the stage's window: a session far behind its calls)
   // from the input ring
   auto row_ok = [&](int32_t g) -> bool {
@@ -271,7 +271,7 @@ __device__ __forceinline__ uint2 sched_control_call(SchedCtl<P>& q, const SchedC
   // load_frame's asserts (sync_layer.rs:218-241) and, with sparse saving, cell.frame == frame_to_load
   auto replay_ok = [&](int32_t from) -> bool {
     if (from == kNull || from >= q.cur || from < q.cur - maxp) return false;
-    return !kSparse || tag(back_slot(q.slot_f, q.cur - from)) == from;
+    return !kSparse || tag(back_slot(q.slot_f, q.cur - from, R)) == from;
   };
 
   uint32_t rec = 0, rec2 = 0, stop = kStopNone;
@@ -430,7 +430,7 @@ __device__ __forceinline__ uint2 sched_control_call(SchedCtl<P>& q, const SchedC
                 if (confirmed >= from && confirmed < q.cur) {
                   rec2 |= (uint32_t)(confirmed - from + 1) << 8;
                   q.last_saved = confirmed;
-                  tag(back_slot(q.slot_f, q.cur - confirmed)) = confirmed;
+                  tag(back_slot(q.slot_f, q.cur - confirmed, R)) = confirmed;
                 }
               } else if (d >= 2) {
                 q.last_saved = q.cur - 1;
@@ -454,7 +454,7 @@ __device__ __forceinline__ uint2 sched_control_call(SchedCtl<P>& q, const SchedC
               q.resim += d2;
               if (confirmed >= q.last_saved && confirmed < q.cur) {
                 rec2 |= (uint32_t)(confirmed - q.last_saved + 1) << 16;
-                tag(back_slot(q.slot_f, q.cur - confirmed)) = confirmed;
+                tag(back_slot(q.slot_f, q.cur - confirmed, R)) = confirmed;
                 q.last_saved = confirmed;
               }
             }
@@ -488,7 +488,7 @@ __device__ __forceinline__ uint2 sched_control_call(SchedCtl<P>& q, const SchedC
               rec |= (adv ? 1u << 7 : 0u) | (save_own ? 1u << 10 : 0u);
               if (adv) {
                 ++q.cur;
-                q.slot_f = next_slot(q.slot_f);
+                q.slot_f = next_slot(q.slot_f, R);
               } else {
                 ++q.skips;
               }
@@ -527,6 +527,30 @@ __device__ inline void sched_report_checksums(const SchedParams& p, int64_t s) {
     const int32_t f = p.rep_frame[i];
     p.rep_ck[i] = f == kNull ? (uint16_t)0 : p.fck[(int64_t)(f & (p.HF - 1)) * p.S + s];
   }
+}
+
+// A launch's start: the control state from HBM (sst), the ring slot of its current frame, the
+// launch's counts at zero; an idle lane (`live` false) runs no call.
+template <int P>
+__device__ inline void sched_load_ctl(const SchedParams& p, SchedCtl<P>& q, int64_t s, bool live) {
+  auto fld = [&](int f) -> int32_t& { return p.sst[(int64_t)f * p.S + s]; };
+  q.cur = fld(kCur);
+  q.lconf = fld(kLconf);
+  q.dframe = fld(kDframe);
+  q.last_saved = fld(kLastSaved);
+  q.delivered = fld(kDelivered);
+  q.local_last = fld(kLocalLast);
+  q.skips = fld(kSkips);
+  q.err = fld(kErr);
+  q.disc = (uint32_t)fld(kDisc);
+  q.last_sent = fld(kLastSent);
+  q.rmask = (uint32_t)fld(kRmask);
+#pragma unroll
+  for (int k = 0; k < P; k++) q.lf[k] = fld(kPl0 + kPlFields * k + 0);
+  if (!live) q.err = 1;
+  q.slot_f = q.cur % p.R;
+  q.rollbacks = 0;
+  q.resim = 0;
 }
 
 // A launch's end: the control state back to HBM (sst), the counts, and -- without sparse saving,
@@ -577,8 +601,7 @@ template <int P, bool kSparse, int kPred, int kLocal, bool kSplit, bool kFeat>
 __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock) void p2p_sched_kernel(SchedParams p) {
   using T = typename InputWord<P>::T;
   using Rec = typename std::conditional<kSparse, uint2, uint32_t>::type;
-  constexpr int F = state_fields(P);
-  constexpr int PC = cell_dwords_s(P) / 4;
+  constexpr int PC = cell_dwords(P) / 4;
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const SchedLds L = sched_lds(P, p.R, kSparse, p.WL, p.K, p.B, kSplit ? 2 : 1);
   int buf = 0;  // this wave's stage buffer
@@ -613,22 +636,14 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock) void p2p_sched_kernel
   const int64_t s = live ? sess0 + lt : sess0;  // idle lanes shadow the block's first session, never store
   const int nb = (int)min((int64_t)kBlock, S - sess0);
   const uint32_t lmask = kLocal >= 0 ? (uint32_t)kLocal : p.local_mask;
-  uint32_t lbytes = 0;
-#pragma unroll
-  for (int k = 0; k < P; k++) lbytes |= ((lmask >> k) & 1u) ? 0xffu << (8 * k) : 0u;
-  const uint32_t rbytes = (P == 4 ? 0xffffffffu : ((1u << (8 * P)) - 1u)) & ~lbytes;  // remote players' bytes
+  const ByteMasks bm = input_byte_masks<P>(lmask);
+  const uint32_t lbytes = bm.lbytes, rbytes = bm.rbytes;
   const int32_t maxp = p.maxp, R = p.R, WL = p.WL;
   const int ring_pieces = R * PC;
 
   // ---- copy in: rings (the block's sessions are contiguous in HBM), tags, local queues
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(p.ring) + sess0 * ring_pieces;
-    const int n = nb * ring_pieces;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-      const int sl = i / ring_pieces, rem = i - sl * ring_pieces;
-      lring[rem * kBlock + sl] = src[i];
-    }
-  }
+  uint4* const gring = reinterpret_cast<uint4*>(p.ring) + sess0 * ring_pieces;
+  ring_to_lds<kBlock, 0>(lring, gring, nb, ring_pieces);
   if (kSparse) {
 #pragma unroll 8
     for (int q = 0; q < R; q++) ltag[q * kBlock + lt] = live ? p.ring_frame[(int64_t)q * S + s] : kNull;
@@ -638,27 +653,10 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock) void p2p_sched_kernel
 
   BoxState<P> st;
   load_state<P>(st, p.cur + s, S);
-  auto fld = [&](int f) -> int32_t& { return p.sst[(int64_t)f * S + s]; };
   // The control state, advanced call by call by the control pass (sched_control_call); the step loop
   // keeps its own copies of what the inputs of a frame depend on.
   SchedCtl<P> q;
-  q.cur = fld(kCur);
-  q.lconf = fld(kLconf);
-  q.dframe = fld(kDframe);
-  q.last_saved = fld(kLastSaved);
-  q.delivered = fld(kDelivered);
-  q.local_last = fld(kLocalLast);
-  q.skips = fld(kSkips);
-  q.err = fld(kErr);
-  q.disc = (uint32_t)fld(kDisc);
-  q.last_sent = fld(kLastSent);
-  q.rmask = (uint32_t)fld(kRmask);
-#pragma unroll
-  for (int k = 0; k < P; k++) q.lf[k] = fld(kPl0 + kPlFields * k + 0);
-  if (!live) q.err = 1;  // idle lanes run no call
-  q.slot_f = q.cur % R;
-  q.rollbacks = 0;
-  q.resim = 0;
+  sched_load_ctl<P>(p, q, s, live);
   int32_t s_cur = q.cur, s_delivered = q.delivered, s_local_last = q.local_last, s_lf[P];
   uint32_t s_disc = q.disc;
   bool s_done = q.err != 0;
@@ -672,32 +670,15 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock) void p2p_sched_kernel
   const SincosConsts K = sincos_consts_vgpr();
   __syncthreads();
 
-  auto next_slot = [&](int32_t x) { return x + 1 == R ? 0 : x + 1; };
-  auto back_slot = [&](int32_t x, int32_t d) { const int32_t y = x - d; return y < 0 ? y + R : y; };
   int32_t s_slot_f = q.slot_f;  // step loop: ring slot of the current frame
-  uint32_t s_last_ck = (uint32_t)fld(kLastCk);  // the display checksum (p.trace_cap > 0)
-  auto cell_load = [&](int32_t slot) {
-#pragma unroll
-    for (int k = 0; k < PC; k++) {
-      const uint4 v = lring[(slot * PC + k) * kBlock + lt];
-      const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-        if (4 * k + i < F) st.w[4 * k + i] = x[i];
-    }
-  };
+  uint32_t s_last_ck = (uint32_t)p.sst[(int64_t)kLastCk * S + s];  // the display checksum (p.trace_cap > 0)
+  auto cell_load = [&](int32_t slot) { cell_unpack<P, kBlock>(st, lring + slot * PC * kBlock + lt); };
   // SaveGameState into `slot` (sync_layer.rs:208-215 + ex_game.rs:103-108); the frame tags and
   // last_saved are the control pass's
   auto save = [&](int32_t slot) {
     const uint32_t ck = fletcher16_state<P>(st);
     if (!kSparse && kFeat && p.interval > 0) p.fck[(int64_t)((int32_t)st.w[0] & (p.HF - 1)) * S + s] = (uint16_t)ck;
-#pragma unroll
-    for (int k = 0; k < PC; k++) {
-      uint32_t x[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) x[i] = 4 * k + i < F ? st.w[4 * k + i] : (4 * k + i == F ? ck : 0u);
-      lring[(slot * PC + k) * kBlock + lt] = make_uint4(x[0], x[1], x[2], x[3]);
-    }
+    cell_pack<P, kBlock>(st, ck, lring + slot * PC * kBlock + lt);
   };
 
   const int32_t c_end = p.c0 + p.n;
@@ -929,7 +910,7 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock) void p2p_sched_kernel
         if (d) {  // adjust_gamestate's LoadGameState (reset_prediction: nothing to reset in the canonical form)
           load = s_cur - d;
           h = load;
-          slot_h = back_slot(s_slot_f, d);
+          slot_h = back_slot(s_slot_f, d, R);
           cell_load(slot_h);
           save_at = kSparse ? (int32_t)((rec2 >> 8) & 0x7fu) : 0;
           replaying = true;
@@ -944,7 +925,7 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock) void p2p_sched_kernel
           if (d2) {  // check_last_saved_state's rollback to the last save
             load = s_cur - d2;
             h = load;
-            slot_h = back_slot(s_slot_f, d2);
+            slot_h = back_slot(s_slot_f, d2, R);
             cell_load(slot_h);
             save_at = (int32_t)((rec2 >> 16) & 0x7fu);
             replaying = true;
@@ -990,11 +971,11 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock) void p2p_sched_kernel
       }
       const bool rep = replaying;
       h = rep ? h + 1 : h;
-      slot_h = rep ? next_slot(slot_h) : slot_h;
+      slot_h = rep ? next_slot(slot_h, R) : slot_h;
       replaying = rep && h != s_cur;
       const bool own_adv = !rep && adv;
       s_cur = own_adv ? s_cur + 1 : s_cur;
-      s_slot_f = own_adv ? next_slot(s_slot_f) : s_slot_f;
+      s_slot_f = own_adv ? next_slot(s_slot_f, R) : s_slot_f;
       c = rep ? c : c + 1;
       at_start = !rep;
     }
@@ -1003,14 +984,7 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock) void p2p_sched_kernel
    if (kSplit) __syncthreads();  // stage it + 1's records ready, stage it's buffers free
   }
   __syncthreads();
-  {  // rings back to HBM
-    uint4* dst = reinterpret_cast<uint4*>(p.ring) + sess0 * ring_pieces;
-    const int n = nb * ring_pieces;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-      const int sl = i / ring_pieces, rem = i - sl * ring_pieces;
-      dst[i] = lring[rem * kBlock + sl];
-    }
-  }
+  ring_from_lds<kBlock, 0>(gring, lring, nb, ring_pieces);  // rings back to HBM
   if (!live) return;
   if (stp_w) {  // the step loop's: the local queues, the game state, the display checksum
     for (int w = 0; w < WL; w++) p.lq[(int64_t)w * S + s] = (uint32_t)llq[w * kBlock + lt];
@@ -1115,7 +1089,7 @@ template <int P, int kPred, int kLocal, bool kFeat>
 __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedParams p) {
   using T = typename InputWord<P>::T;
   constexpr int F = state_fields(P);
-  constexpr int PC = cell_dwords_s(P) / 4;
+  constexpr int PC = cell_dwords(P) / 4;
   const int TW = p.TW;  // table frames (a power of two)
   const ChainLds L = chain_lds(P, p.R, TW, p.K, p.B);
 #define lring (reinterpret_cast<uint4*>(sched_lds_base))
@@ -1128,10 +1102,8 @@ __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedPa
   const int nb = (int)min((int64_t)kCS, S - sess0);
   const bool ctl_w = threadIdx.x >= kCS * kSL;
   const uint32_t lmask = kLocal >= 0 ? (uint32_t)kLocal : p.local_mask;
-  uint32_t lbytes = 0;
-#pragma unroll
-  for (int k = 0; k < P; k++) lbytes |= ((lmask >> k) & 1u) ? 0xffu << (8 * k) : 0u;
-  const uint32_t rbytes = (P == 4 ? 0xffffffffu : ((1u << (8 * P)) - 1u)) & ~lbytes;
+  const ByteMasks bm = input_byte_masks<P>(lmask);
+  const uint32_t lbytes = bm.lbytes, rbytes = bm.rbytes;
   const int32_t maxp = p.maxp, R = p.R;
   const int ring_pieces = R * PC;
   const int32_t c_end = p.c0 + p.n;
@@ -1139,17 +1111,11 @@ __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedPa
   auto tab0 = [&](int32_t f, int col) -> uint4& { return ltab[((f & (TW - 1)) * kCS + col) * 2]; };
   auto tab1 = [&](int32_t f, int col) -> uint4& { return ltab[((f & (TW - 1)) * kCS + col) * 2 + 1]; };
   auto stage_lo = [&](int st) { return max(0, p.c0 + st * p.K - p.B); };
-  auto stage_rows = [&](int st) -> T* { return reinterpret_cast<T*>(sched_lds_base + L.o_rows + (st % 3) * L.rows_b); };
+  auto rows_of_stage = [&](int st) -> T* { return reinterpret_cast<T*>(sched_lds_base + L.o_rows + (st % 3) * L.rows_b); };
 
   // ---- copy in: the block's rings
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(p.ring) + sess0 * ring_pieces;
-    const int n = nb * ring_pieces;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-      const int sl = i / ring_pieces, rem = i - sl * ring_pieces;
-      lring[rem * kCS + sl] = src[i];
-    }
-  }
+  uint4* const gring = reinterpret_cast<uint4*>(p.ring) + sess0 * ring_pieces;
+  ring_to_lds<kCS, 0>(lring, gring, nb, ring_pieces);
 
   if (ctl_w) {
     // ================= the control wave: lanes 0..15 are the block's sessions =================
@@ -1157,25 +1123,8 @@ __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedPa
     const int col = lt < kCS ? lt : 0;
     const bool live = lt < nb;
     const int64_t s = live ? sess0 + lt : sess0;
-    auto fld = [&](int f) -> int32_t { return p.sst[(int64_t)f * S + s]; };
     SchedCtl<P> q;
-    q.cur = fld(kCur);
-    q.lconf = fld(kLconf);
-    q.dframe = fld(kDframe);
-    q.last_saved = fld(kLastSaved);
-    q.delivered = fld(kDelivered);
-    q.local_last = fld(kLocalLast);
-    q.skips = fld(kSkips);
-    q.err = fld(kErr);
-    q.disc = (uint32_t)fld(kDisc);
-    q.last_sent = fld(kLastSent);
-    q.rmask = (uint32_t)fld(kRmask);
-#pragma unroll
-    for (int k = 0; k < P; k++) q.lf[k] = fld(kPl0 + kPlFields * k + 0);
-    if (!live) q.err = 1;  // idle lanes run no call
-    q.slot_f = q.cur % R;
-    q.rollbacks = 0;
-    q.resim = 0;
+    sched_load_ctl<P>(p, q, s, live);
     const int32_t cur0 = q.cur;
     int32_t own_hi = cur0 - 1, minpre = INT32_MAX, tn = 0, nchain = 0, last_m = kNull, dups = 0;
     bool started = false;
@@ -1228,7 +1177,7 @@ __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedPa
     auto store = [&](int st) -> bool {
       const int32_t cs = p.c0 + st * p.K, ce = min(c_end, cs + p.K), lo = stage_lo(st);
       const int nrows = ce - lo, ncalls = ce - cs;
-      T* lrows = stage_rows(st);
+      T* lrows = rows_of_stage(st);
       int32_t* lrowtag = reinterpret_cast<int32_t*>(sched_lds_base + L.o_rowtag + (st % 3) * L.rowtag_b);
       int32_t* larr = reinterpret_cast<int32_t*>(sched_lds_base + L.o_arr + (st & 1) * L.arr_b);
       uint8_t* lev = sched_lds_base + L.o_ev + (st & 1) * L.ev_b;
@@ -1347,7 +1296,7 @@ __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedPa
         const int32_t lo = stage_lo(it);
         const int nrows = ce - lo;
         const uint32_t o_rowtag = L.o_rowtag + (it % 3) * L.rowtag_b, o_rows = L.o_rows + (it % 3) * L.rows_b;
-        const T* lrows = stage_rows(it);
+        const T* lrows = rows_of_stage(it);
         const int32_t* larr = reinterpret_cast<const int32_t*>(sched_lds_base + L.o_arr + (it & 1) * L.arr_b);
         const uint8_t* lev = sched_lds_base + L.o_ev + (it & 1) * L.ev_b;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // this stage's staging visible to the wave
@@ -1500,14 +1449,7 @@ __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedPa
     }
     __syncthreads();  // (3) every step done
     // rings back (every thread), then this session's control state and local queue
-    {
-      uint4* dst = reinterpret_cast<uint4*>(p.ring) + sess0 * ring_pieces;
-      const int n = nb * ring_pieces;
-      for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int sl = i / ring_pieces, rem = i - sl * ring_pieces;
-        dst[i] = lring[rem * kCS + sl];
-      }
-    }
+    ring_from_lds<kCS, 0>(gring, lring, nb, ring_pieces);
     if (!live || lt >= kCS) return;
     if (q.local_last != kNull)
       for (int32_t f = max(0, q.cur - maxp - 1); f <= q.local_last; f++)
@@ -1617,30 +1559,13 @@ __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedPa
           for (int k = 0; k < F; k++) st.w[k] = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)st.w[k]);
         }
         if (__builtin_amdgcn_ballot_w64(ring_ld)) {
-          if (ring_ld) {
-#pragma unroll
-            for (int k = 0; k < PC; k++) {
-              const uint4 v = lring[(slot_tau * PC + k) * kCS + sib];
-              const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-              for (int i = 0; i < 4; i++)
-                if (4 * k + i < F) st.w[4 * k + i] = x[i];
-            }
-          }
+          if (ring_ld) cell_unpack<P, kCS>(st, lring + slot_tau * PC * kCS + sib);
         }
         // SaveGameState of frame tau (sync_layer.rs:208-215, ex_game.rs:103-108)
         {
           const uint32_t ck = fletcher16_state<P>(st);
           if (kFeat && wr && p.interval > 0) p.fck[(int64_t)(tau & (p.HF - 1)) * S + s] = (uint16_t)ck;
-          if (wr) {
-#pragma unroll
-            for (int k = 0; k < PC; k++) {
-              uint32_t x[4];
-#pragma unroll
-              for (int i = 0; i < 4; i++) x[i] = 4 * k + i < F ? st.w[4 * k + i] : (4 * k + i == F ? ck : 0u);
-              lring[(slot_tau * PC + k) * kCS + sib] = make_uint4(x[0], x[1], x[2], x[3]);
-            }
-          }
+          if (wr) cell_pack<P, kCS>(st, ck, lring + slot_tau * PC * kCS + sib);
         }
         if (adv) {
           if (kLean) advance_state_lean_k<P>(st, in, K);
@@ -1650,7 +1575,7 @@ __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedPa
         e1 = n1;
         act = act & !(on & (tau >= cend));  // handed off this step (the lineage read it above)
         tau = tau1;
-        slot_tau = on ? (slot_tau + 1 == R ? 0 : slot_tau + 1) : slot_tau;
+        slot_tau = on ? next_slot(slot_tau, R) : slot_tau;
       }
       };
       if (lean_ok) steps(std::true_type());
@@ -1659,14 +1584,7 @@ __global__ __launch_bounds__(kChainThreads) void p2p_sched_chains_kernel(SchedPa
     __syncthreads();  // (2)
   }
   __syncthreads();  // (3)
-  {
-    uint4* dst = reinterpret_cast<uint4*>(p.ring) + sess0 * ring_pieces;
-    const int n = nb * ring_pieces;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-      const int sl = i / ring_pieces, rem = i - sl * ring_pieces;
-      dst[i] = lring[rem * kCS + sl];
-    }
-  }
+  ring_from_lds<kCS, 0>(gring, lring, nb, ring_pieces);
   if (live && j == 0) store_state<P>(st, p.cur + s, S);
 #undef lring
 #undef ltab
