@@ -24,6 +24,7 @@ GGRS_E_TOO_FAR_BEHIND = -5
 GGRS_PACKET_NO_REFERENCE, GGRS_PACKET_STOPPED = -16, -17  # ggrs_p2p_read_packet_results's own status codes
 GGRS_EMIT_CLOSED, GGRS_EMIT_DISCONNECTED = -18, -19  # ggrs_p2p_read_emit_state's status
 GGRS_EMIT_ROW_LOST = -20  # ggrs_p2p_read_spectator_emit_state's own status
+GGRS_TIME_SYNC_KEEP = -2 ** 31  # ggrs_p2p_time_sync's remote_advantage: no report at this call
 NULL_FRAME = -1
 REQ_SAVE, REQ_LOAD, REQ_ADVANCE = 0, 1, 2
 STATUS_CONFIRMED, STATUS_PREDICTED, STATUS_DISCONNECTED = 0, 1, 2
@@ -66,6 +67,7 @@ EXPORTS = (
     "ggrs_p2p_set_packet_feed", "ggrs_p2p_receive_packets", "ggrs_p2p_read_packet_results",
     "ggrs_p2p_set_packet_emit", "ggrs_p2p_emit_packets", "ggrs_p2p_read_emit_state",
     "ggrs_p2p_set_spectator_emit", "ggrs_p2p_emit_spectator_packets", "ggrs_p2p_read_spectator_emit_state",
+    "ggrs_p2p_set_time_sync", "ggrs_p2p_time_sync", "ggrs_p2p_read_time_sync_state",
     "ggrs_spectator_engine_create", "ggrs_spectator_engine_destroy", "ggrs_spectator_engine_config",
     "ggrs_spectator_add_inputs", "ggrs_spectator_add_arrivals", "ggrs_spectator_advance_frames",
     "ggrs_spectator_calls", "ggrs_spectator_synchronize", "ggrs_spectator_read_sessions",

@@ -72,18 +72,26 @@ struct PacketEmitState {
   // to launch.
   int check_calls(int32_t first_call, int32_t n, int32_t current_frame, int32_t oldest_held, int32_t cap, const EmitIo& io,
                   int32_t on_device) const {
+    if (int rc = check_order(first_call, n, current_frame, oldest_held, cap, !io.start || !io.len || !io.word || !io.packets))
+      return rc;
+    if (n > 0 && on_device && ((uintptr_t)io.packets & 3))
+      return set_error(GGRS_E_INVALID, "device packets must be dword aligned");
+    return GGRS_OK;
+  }
+  // ... the order alone (time sync, p2p_time_sync.hip, walks the same calls by the same rule): null_arg
+  // says an output array is missing, `what` names the caller in the order error
+  int check_order(int32_t first_call, int32_t n, int32_t current_frame, int32_t oldest_held, int32_t cap, bool null_arg,
+                  const char* what = "packets are emitted") const {
     if (n < 0) return set_error(GGRS_E_INVALID, "n_calls must be >= 0");
     if (first_call != next)
-      return set_error(GGRS_E_INVALID, "packets are emitted in call order, each call once (expected call %d, got %d)", next,
-                       first_call);
+      return set_error(GGRS_E_INVALID, "%s in call order, each call once (expected call %d, got %d)", what, next, first_call);
     if (n == 0) return GGRS_OK;
-    if (!io.start || !io.len || !io.word || !io.packets) return set_error(GGRS_E_INVALID, "null argument");
+    if (null_arg) return set_error(GGRS_E_INVALID, "null argument");
     if ((int64_t)first_call + n > current_frame)
       return set_error(GGRS_E_INVALID, "calls up to %d are emitted after they ran (%d calls run)", first_call + n - 1,
                        current_frame);
     if (first_call < oldest_held)
       return set_error(GGRS_E_INVALID, "call %d is no longer held (the last %d calls' rows are)", first_call, cap);
-    if (on_device && ((uintptr_t)io.packets & 3)) return set_error(GGRS_E_INVALID, "device packets must be dword aligned");
     return GGRS_OK;
   }
   // The arrays the kernel takes for the caller's `io`: the caller's own when they are on the device,
@@ -211,6 +219,13 @@ struct ggrs_p2p_engine {
   uint32_t* spec_ring = nullptr;    // [spec_q][S] every player's confirmed byte of frame f, slot f & (spec_q - 1)
   int32_t* spec_st = nullptr;       // [kSpecFields][S] the session's words (SpecField)
   int32_t* spec_ep = nullptr;       // [kSpecEpFields][spec_k][S] the endpoints' words (SpecEpField)
+  // time sync (ggrs_p2p_set_time_sync; p2p_time_sync.hip): the endpoint's TimeSync windows, frames_ahead and
+  // the wait recommendation per call; reads emit_ll as the two emits do (tsync: the mode, the next call
+  // and the staging of host-sourced calls -- its max_pending and stride are unused)
+  ggrs::PacketEmitState tsync;
+  int32_t tsync_fps = 0;
+  int32_t* tsync_win = nullptr;     // [2][kTsWindow][S] the local and the remote window
+  int32_t* tsync_st = nullptr;      // [kTsFields][S] the endpoint's time-sync words (TsField)
   ggrs::SpanTimer timer;
 };
 
@@ -246,11 +261,25 @@ enum SpecEpField : int {
   kSpecEpClosedCall,   // the call that closed the endpoint (-1)
   kSpecEpFields
 };
+// time sync: FRAME_WINDOW_SIZE (time_sync.rs:3); the per-session words kept between launches
+constexpr int kTsWindow = 30;
+enum TsField : int {
+  kTsRtt = 0,      // round_trip_time, ms
+  kTsRemote,       // remote_frame_advantage
+  kTsLocal,        // local_frame_advantage
+  kTsNextSleep,    // next_recommended_sleep
+  kTsClosedCall,   // the call that closed the endpoint (-1: open)
+  kTsLlPrev,       // the local players' last queued frame after the last call taken
+  kTsRecv,         // the endpoint's last_recv_frame after it
+  kTsFields
+};
+// p2p_time_sync.hip: free time sync's own buffers (emit_ll is p2p_emit_free's)
+int p2p_time_sync_free(ggrs_p2p_engine* e);
 // p2p_emit.hip: free packet emit's buffers and emit_ll (the engine's destruction: after p2p_spec_emit_free)
 int p2p_emit_free(ggrs_p2p_engine* e);
 // p2p_spec_emit.hip: free spectator emit's own buffers (emit_ll is p2p_emit_free's)
 int p2p_spec_emit_free(ggrs_p2p_engine* e);
-// emit_ll, shared by the two emits: allocated by the first configured, every row "nothing queued"
+// emit_ll, shared by the two emits and time sync: allocated by the first configured, every row "nothing queued"
 int p2p_emit_ll_alloc(ggrs_p2p_engine* e);
 
 // What an emit kernel's parameters take from the engine for a launch of calls c0 .. c0 + n - 1: the

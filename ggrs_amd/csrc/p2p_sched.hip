@@ -94,7 +94,7 @@ struct SchedParams {
   // it (ex_game.rs:115-127), the previous call's when it advanced nothing
   uint16_t* trace;
   int32_t trace_cap;
-  // packet emit and spectator emit (p2p_emit.hip, p2p_spec_emit.hip; emit != 0): per call c (row c % cap) and session the local players'
+  // packet emit, spectator emit and time sync (p2p_emit.hip, p2p_spec_emit.hip, p2p_time_sync.hip; emit != 0): per call c (row c % cap) and session the local players'
   // last queued frame after it -- the call queued a frame when it rose -- or kEmitStopped from the
   // call that stopped the session
   int32_t* emit_ll;
@@ -1763,7 +1763,7 @@ int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n) {
   p.trace = e->trace;
   p.trace_cap = e->trace ? e->cfg.trace_capacity : 0;
   p.emit_ll = e->emit_ll;
-  p.emit = e->emit.on || e->spec.on;  // (spectator emit reads the same row)
+  p.emit = e->emit.on || e->spec.on || e->tsync.on;  // (spectator emit and time sync read the same row)
   SchedPlanIn in{};
   in.sessions = p.S;
   in.players = e->cfg.num_players;
@@ -1817,6 +1817,7 @@ int ggrs_p2p_set_arrival_schedule(ggrs_p2p_engine_t* e, int32_t on) {
     e->pkt = 0;  // (the packet feed is a form of the arrival schedules)
     e->emit.on = 0;  // (and so is packet emit)
     e->spec.on = 0;  // (and spectator emit)
+    e->tsync.on = 0;  // (and time sync)
     return GGRS_OK;
   }
   if (e->cfg.max_prediction + e->cfg.input_delay + 2 >= kQ)
@@ -1877,9 +1878,9 @@ int ggrs_p2p_add_arrivals(ggrs_p2p_engine_t* e, int32_t first_call, int32_t n, c
 int ggrs_p2p_add_peer_reports(ggrs_p2p_engine_t* e, int32_t first_call, int32_t n, const int32_t* reports) {
   if (!e || (!reports && n > 0)) return set_error(GGRS_E_INVALID, "null argument");
   if (!e->sched) return set_error(GGRS_E_STATE, "peer reports need ggrs_p2p_set_arrival_schedule(e, 1)");
-  if (e->spec.on)
-    return set_error(GGRS_E_STATE, "peer reports with spectator emit are not supported (the emit restates the connect "
-                                   "status from the events alone)");
+  if (e->spec.on || e->tsync.on)
+    return set_error(GGRS_E_STATE, "peer reports with spectator emit or time sync are not supported (they restate the "
+                                   "connect status from the events alone)");
   if (n < 0 || first_call < e->current_frame || first_call + n > e->next_arrival_call)
     return set_error(GGRS_E_INVALID, "peer reports are for calls not yet run whose arrivals were added (calls %d .. %d)",
                      e->current_frame, e->next_arrival_call - 1);

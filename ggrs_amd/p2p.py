@@ -79,6 +79,9 @@ def _bind(L):
     L.ggrs_p2p_set_spectator_emit.argtypes = [vp, i32, i32, i32]
     L.ggrs_p2p_emit_spectator_packets.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
     L.ggrs_p2p_read_spectator_emit_state.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ggrs_p2p_set_time_sync.argtypes = [vp, i32]
+    L.ggrs_p2p_time_sync.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32]
+    L.ggrs_p2p_read_time_sync_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     for name in _lib.EXPORTS:
         if name.startswith("ggrs_p2p_"):
             getattr(L, name).restype = ctypes.c_int
@@ -405,6 +408,38 @@ class P2PEngine:
         S, K = self.num_sessions, getattr(self, "num_spectators", 1)
         out = [np.zeros(S, np.int32)] + [np.zeros((K, S), np.int32) for _ in range(4)]
         _lib.check(self._L.ggrs_p2p_read_spectator_emit_state(self._h, *(_vp(a) for a in out)))
+        return tuple(out)
+
+    # ---- time sync (include/ggrs_amd.h, ggrs_p2p_*time_sync*; p2p_time_sync.hip)
+    def set_time_sync(self, fps=60):
+        """Every session's frames_ahead and WaitRecommendation are computed on the device (time_sync);
+        after set_arrival_schedule, before the first call.  fps in 1..1000 (the reference's default)."""
+        _lib.check(self._L.ggrs_p2p_set_time_sync(self._h, fps))
+        self.fps = fps
+
+    def time_sync(self, first_call, n_calls, rtt_ms=None, remote_advantage=None, out=None):
+        """Time sync of calls first_call .. first_call + n_calls - 1 (already run, taken in order, each
+        once): rtt_ms [n][S] int32 (the round trip a QualityReply measured at the call, negative: none)
+        and remote_advantage [n][S] int32 (the frame_advantage of a QualityReport received at the call,
+        GGRS_TIME_SYNC_KEEP: none) or None.  Returns (local_advantage, frames_ahead, skip_frames) [n][S]
+        int32 as numpy arrays -- or, with out = such a tuple of torch tensors on the engine's device
+        (rtt_ms and remote_advantage then device tensors too), fills and returns them; the launch runs
+        on the engine's stream (synchronize() before another stream reads).  skip_frames > 0 is the
+        call's GgrsEvent::WaitRecommendation."""
+        n, S = int(n_calls), self.num_sessions
+        dev = out is not None
+        outs = list(out) if dev else [np.zeros((n, S), np.int32) for _ in range(3)]
+        ptrs, keep = _lib.marshal([rtt_ms, remote_advantage] + outs, ((n, S),) * 5, ("int32",) * 5, dev)
+        _lib.check(self._L.ggrs_p2p_time_sync(self._h, first_call, n, *ptrs, int(dev)))
+        return tuple(outs)
+
+    def time_sync_state(self):
+        """(local_advantage, remote_advantage, rtt_ms, next_recommended_sleep, closed_call) [S] int32
+        each (closed_call -1: the endpoint is open) and windows [2][30][S] int32, the local window then
+        the remote one."""
+        S = self.num_sessions
+        out = [np.zeros(S, np.int32) for _ in range(5)] + [np.zeros((2, 30, S), np.int32)]
+        _lib.check(self._L.ggrs_p2p_read_time_sync_state(self._h, *(_vp(a) for a in out)))
         return tuple(out)
 
     KERNEL_FORMS = {"default": 0, "unstaged": 1, "lockstep": 2, "flat": 3, "chains": 4, "flat_queues": 5,

@@ -780,6 +780,66 @@ int ggrs_p2p_emit_spectator_packets(ggrs_p2p_engine_t* eng, int32_t first_call, 
 int ggrs_p2p_read_spectator_emit_state(ggrs_p2p_engine_t* eng, int32_t* next_spectator_frame, int32_t* last_acked,
                                        int32_t* pending, int32_t* status, int32_t* closed_call);
 
+/* ---- Time sync: every session's P2PSession::frames_ahead() and GgrsEvent::WaitRecommendation, per
+ * call, on the device: check_wait_recommendation (p2p_session.rs:357, :804-817) over max_frame_advantage
+ * (:786-802), the endpoint's TimeSync window (time_sync.rs:25-39), update_local_frame_advantage
+ * (protocol.rs:260-269, from poll_remote_clients, p2p_session.rs:442-447), on_quality_report
+ * (protocol.rs:649-653), on_quality_reply and the window push inside send_input (:433-437).  One
+ * endpoint per session holds all of its remote players, as in packet emit.  Arrival-schedule mode is
+ * required; lockstep mode, the packet feed and the two emits combine with it; peers' disconnect reports
+ * do not (GGRS_E_STATE from whichever comes second: the connect status is restated from the events bits
+ * alone).  Per session round_trip_time (ms), remote_frame_advantage, local_frame_advantage and
+ * next_recommended_sleep start at 0, the two windows of 30 entries at zeros, the endpoint open.  Call c,
+ * after it ran:
+ *  1. a session that stopped (an error in ggrs_p2p_read_sessions) takes no step from its stopping call
+ *     on: frames_ahead 0, skip_frames 0, local_advantage its last value;
+ *  2. while the endpoint is open, rtt_ms[c] >= 0 sets round_trip_time (a negative value keeps it; values
+ *     above 1 << 20 are clamped there -- divergence: the reference overflows only beyond i32, the clamp
+ *     keeps ping * fps inside i32), and remote_advantage[c] != GGRS_TIME_SYNC_KEEP sets
+ *     remote_frame_advantage, clamped to the i16 range as send_quality_report clamps what it sends
+ *     (protocol.rs:504-508) -- so one engine's local_advantage row is its peer's remote_advantage row;
+ *  3. while the endpoint is open and last_recv_frame != GGRS_NULL_FRAME: local_frame_advantage =
+ *     last_recv_frame + ((round_trip_time / 2) * fps) / 1000 - current_frame, with current_frame that of
+ *     the call's start and last_recv_frame the endpoint's after the call's poll (ack_frame of
+ *     ggrs_p2p_emit_packets);
+ *  4. an Event::Disconnected bit of a remote player at call c closes the endpoint from here on
+ *     (disconnect_player_at_frame, :618-655): nothing is taken in or pushed any more;
+ *  5. frames_ahead[c] = average_frame_advantage() while the endpoint is open, else 0: from the windows
+ *     before this call's push, in f32 as time_sync.rs:30-39 (local_sum / 30.0, remote_sum / 30.0,
+ *     (remote_avg - local_avg) / 2.0 truncated).  If current_frame > next_recommended_sleep and
+ *     frames_ahead >= 3 (MIN_RECOMMENDATION): next_recommended_sleep = current_frame + 60
+ *     (RECOMMENDATION_INTERVAL) and skip_frames[c] = frames_ahead; else skip_frames[c] = 0;
+ *  6. while the endpoint is open and the call's add_local_input was accepted:
+ *     local[(current_frame + input_delay) % 30] = local_frame_advantage, remote[...] =
+ *     remote_frame_advantage;
+ *  7. local_advantage[c] = local_frame_advantage after the call: NetworkStats::local_frames_behind, and
+ *     what a QualityReport sent at this call carries.
+ * Not built: the recommendation is reported, not enacted (every session of an engine takes every call);
+ * the QualityReport / QualityReply messages, their 200 ms timer and the rest of the envelope stay with
+ * the host, as do NetworkStats' send_queue_len and kbps_sent; fixed-latency engines and peer reports.
+ * The scheduled kernels store what they store for packet emit, one word per session and call.
+ * Kernel: p2p_time_sync.hip. */
+#define GGRS_TIME_SYNC_KEEP INT32_MIN /* remote_advantage: no QualityReport arrived at this call */
+/* Part of the configuration (after ggrs_p2p_set_arrival_schedule(eng, 1), before the first call and
+ * before any peer report; a local and a remote player): fps in 1..1000 (the reference's default: 60;
+ * GGRS_E_INVALID otherwise).  GGRS_E_STATE after the first call, on a fixed-latency engine and with peer
+ * reports. */
+int ggrs_p2p_set_time_sync(ggrs_p2p_engine_t* eng, int32_t fps);
+/* Calls first_call .. first_call + n_calls - 1: already run, in order, each exactly once, still among
+ * the last input_capacity calls (GGRS_E_INVALID otherwise).  rtt_ms [n][S] and remote_advantage [n][S]
+ * may be NULL (nothing arrived).  Outputs [n][S] each: local_advantage, frames_ahead, skip_frames.
+ * on_device as ggrs_p2p_emit_packets.  The result does not depend on how the calls are split over
+ * invocations.  GGRS_E_STATE without ggrs_p2p_set_time_sync. */
+int ggrs_p2p_time_sync(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, const int32_t* rtt_ms,
+                       const int32_t* remote_advantage, int32_t* local_advantage, int32_t* frames_ahead,
+                       int32_t* skip_frames, int32_t on_device);
+/* Per session, [num_sessions] each: local_frame_advantage, remote_frame_advantage, round_trip_time,
+ * next_recommended_sleep and the call at which the endpoint closed (-1: open); windows [2][30][S], the
+ * local window then the remote one.  Any pointer may be NULL. */
+int ggrs_p2p_read_time_sync_state(ggrs_p2p_engine_t* eng, int32_t* local_advantage, int32_t* remote_advantage,
+                                  int32_t* rtt_ms, int32_t* next_recommended_sleep, int32_t* closed_call,
+                                  int32_t* windows);
+
 /* ---------------------------------------------------------------------------------------------
  * Spectators: num_sessions independent SpectatorSessions (src/sessions/p2p_spectator_session.rs),
  * each following one host's confirmed input stream over its own network, each call =

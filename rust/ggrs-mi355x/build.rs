@@ -32,6 +32,7 @@ const UNITS: &[(&str, &[&str])] = &[
     ("p2p_emit.hip", NONE),
     ("spectator_ingest.hip", NONE),
     ("p2p_spec_emit.hip", NONE),
+    ("p2p_time_sync.hip", NONE),
 ];
 
 fn main() {

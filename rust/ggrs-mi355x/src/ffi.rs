@@ -56,6 +56,7 @@ pub const GGRS_PACKET_STOPPED: i32 = -17;
 pub const GGRS_EMIT_CLOSED: i32 = -18;
 pub const GGRS_EMIT_DISCONNECTED: i32 = -19;
 pub const GGRS_EMIT_ROW_LOST: i32 = -20;
+pub const GGRS_TIME_SYNC_KEEP: i32 = i32::MIN;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -394,6 +395,28 @@ extern "C" {
         pending: *mut i32,
         status: *mut i32,
         closed_call: *mut i32,
+    ) -> i32;
+    // time sync (p2p_time_sync.hip): frames_ahead and the wait recommendation per call, on the device
+    pub fn ggrs_p2p_set_time_sync(eng: *mut ggrs_p2p_engine_t, fps: i32) -> i32;
+    pub fn ggrs_p2p_time_sync(
+        eng: *mut ggrs_p2p_engine_t,
+        first_call: i32,
+        n_calls: i32,
+        rtt_ms: *const i32,
+        remote_advantage: *const i32,
+        local_advantage: *mut i32,
+        frames_ahead: *mut i32,
+        skip_frames: *mut i32,
+        on_device: i32,
+    ) -> i32;
+    pub fn ggrs_p2p_read_time_sync_state(
+        eng: *mut ggrs_p2p_engine_t,
+        local_advantage: *mut i32,
+        remote_advantage: *mut i32,
+        rtt_ms: *mut i32,
+        next_recommended_sleep: *mut i32,
+        closed_call: *mut i32,
+        windows: *mut i32,
     ) -> i32;
 
     // ---- spectators (src/sessions/p2p_spectator_session.rs), batched
