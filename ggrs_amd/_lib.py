@@ -25,6 +25,7 @@ GGRS_PACKET_NO_REFERENCE, GGRS_PACKET_STOPPED = -16, -17  # ggrs_p2p_read_packet
 GGRS_EMIT_CLOSED, GGRS_EMIT_DISCONNECTED = -18, -19  # ggrs_p2p_read_emit_state's status
 GGRS_EMIT_ROW_LOST = -20  # ggrs_p2p_read_spectator_emit_state's own status
 GGRS_TIME_SYNC_KEEP = -2 ** 31  # ggrs_p2p_time_sync's remote_advantage: no report at this call
+GGRS_DESYNC_ROW_LOST = -21  # ggrs_p2p_read_desync_state's status
 NULL_FRAME = -1
 REQ_SAVE, REQ_LOAD, REQ_ADVANCE = 0, 1, 2
 STATUS_CONFIRMED, STATUS_PREDICTED, STATUS_DISCONNECTED = 0, 1, 2
@@ -68,6 +69,8 @@ EXPORTS = (
     "ggrs_p2p_set_packet_emit", "ggrs_p2p_emit_packets", "ggrs_p2p_read_emit_state",
     "ggrs_p2p_set_spectator_emit", "ggrs_p2p_emit_spectator_packets", "ggrs_p2p_read_spectator_emit_state",
     "ggrs_p2p_set_time_sync", "ggrs_p2p_time_sync", "ggrs_p2p_read_time_sync_state",
+    "ggrs_p2p_set_desync_compare", "ggrs_p2p_add_remote_reports", "ggrs_p2p_add_remote_reports_from",
+    "ggrs_p2p_compare_reports", "ggrs_p2p_read_desync_events", "ggrs_p2p_read_desync_state",
     "ggrs_spectator_engine_create", "ggrs_spectator_engine_destroy", "ggrs_spectator_engine_config",
     "ggrs_spectator_add_inputs", "ggrs_spectator_add_arrivals", "ggrs_spectator_advance_frames",
     "ggrs_spectator_calls", "ggrs_spectator_synchronize", "ggrs_spectator_read_sessions",

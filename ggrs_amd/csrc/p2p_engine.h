@@ -2,7 +2,8 @@
 // desync detection, lockstep) and p2p_sched.hip (scheduled arrivals: per-session remote-arrival
 // tables, the prediction threshold and disconnects) and p2p_ingest.hip (the packet feed of the
 // scheduled mode) and p2p_emit.hip (its send side) and p2p_spec_emit.hip (the send side towards the
-// sessions' spectators), with the host side the two send sides share (PacketEmitState: configuration
+// sessions' spectators), p2p_time_sync.hip and p2p_desync.hip (time sync and the checksum comparison,
+// which walk the same calls by the same order rule), with the host side the two send sides share (PacketEmitState: configuration
 // and call-order checks, the staging of a launch's arrays, the group plan; emit_begin / emit_end: an
 // emit call before and after the unit's kernel launch; EmitCalls: what emit_begin hands the unit for
 // its kernel's parameters).  Host code and plain structs only; no kernels here.
@@ -226,6 +227,22 @@ struct ggrs_p2p_engine {
   int32_t tsync_fps = 0;
   int32_t* tsync_win = nullptr;     // [2][kTsWindow][S] the local and the remote window
   int32_t* tsync_st = nullptr;      // [kTsFields][S] the endpoint's time-sync words (TsField)
+  // checksum comparison (ggrs_p2p_set_desync_compare; p2p_desync.hip): the peer's report rows, the two
+  // tables of UdpProtocol::on_checksum_report and compare_local_checksums_against_peers, the events
+  // (dcmp: the mode and the next call -- its staging holds host-sourced peer rows)
+  ggrs::PacketEmitState dcmp;
+  int32_t dcmp_interval = 0;        // the interval it was configured with
+  int32_t dcmp_max_events = 0;
+  int32_t dcmp_added = 0;           // the peer's rows added so far
+  int32_t* dcmp_peer_frame = nullptr;  // [cap][S] the peer's report rows, row g % cap: the frame (-1 none),
+  uint16_t* dcmp_peer_ck = nullptr;    // ... its checksum
+  int32_t* dcmp_peer_ll = nullptr;     // ... and the peer's last queued local frame after its call g
+  int32_t* dcmp_frames = nullptr;   // [2][kDcTable][S] local_checksum_history's then pending_checksums' frames
+  uint16_t* dcmp_cks = nullptr;     // [2][kDcTable][S] ... and checksums
+  int32_t* dcmp_st = nullptr;       // [kDcFields][S] the session's words (DcField)
+  int32_t* dcmp_events = nullptr;   // [4][max_events] call, session, frame, local | remote << 16
+  unsigned long long* dcmp_count = nullptr;  // the events raised (exact past max_events)
+  hipEvent_t dcmp_sync[2] = {nullptr, nullptr};  // ggrs_p2p_add_remote_reports_from: the two streams' order
   ggrs::SpanTimer timer;
 };
 
@@ -273,6 +290,25 @@ enum TsField : int {
   kTsRecv,         // the endpoint's last_recv_frame after it
   kTsFields
 };
+// checksum comparison: MAX_CHECKSUM_HISTORY_SIZE (protocol.rs:27); the per-session words kept between launches
+constexpr int kDcTable = 32;
+enum DcField : int {
+  kDcCursor = 0,   // the peer's rows delivered so far
+  kDcNewest,       // the newest frame received from the peer (NULL_FRAME)
+  kDcRecv,         // the endpoint's last_recv_frame after the last call compared
+  kDcStatus,       // 0, GGRS_DESYNC_ROW_LOST
+  kDcHist,         // entries of local_checksum_history
+  kDcPend,         // entries of pending_checksums
+  kDcRefused,      // reports refused
+  kDcEvents,       // DesyncDetected events raised
+  kDcFirstCall,    // the first event's call (-1), frame (-1), local and remote checksum
+  kDcFirstFrame,
+  kDcFirstLocal,
+  kDcFirstRemote,
+  kDcFields
+};
+// p2p_desync.hip: free the checksum comparison's buffers
+int p2p_desync_free(ggrs_p2p_engine* e);
 // p2p_time_sync.hip: free time sync's own buffers (emit_ll is p2p_emit_free's)
 int p2p_time_sync_free(ggrs_p2p_engine* e);
 // p2p_emit.hip: free packet emit's buffers and emit_ll (the engine's destruction: after p2p_spec_emit_free)

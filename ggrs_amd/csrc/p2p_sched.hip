@@ -1818,6 +1818,7 @@ int ggrs_p2p_set_arrival_schedule(ggrs_p2p_engine_t* e, int32_t on) {
     e->emit.on = 0;  // (and so is packet emit)
     e->spec.on = 0;  // (and spectator emit)
     e->tsync.on = 0;  // (and time sync)
+    e->dcmp.on = 0;  // (and the checksum comparison)
     return GGRS_OK;
   }
   if (e->cfg.max_prediction + e->cfg.input_delay + 2 >= kQ)

@@ -246,3 +246,66 @@ class SchedDesyncDetector:
             del self.remote[:done - self.remote_base]
             self.remote_base = done
         return events
+
+
+class DeviceDesyncDetector:
+    """SchedDesyncDetector's surface over the device's checksum comparison
+    (ggrs_p2p_set_desync_compare, p2p_desync.hip): the pending reports, the history and the comparison
+    of every session stay in device memory, and poll() reads back only the events.  Created after
+    engine.set_arrival_schedule(True), before the first call.  The arrival rows are the engine's own
+    (note_arrivals is accepted and ignored); poll() needs the peer's rows of every call but the last
+    one run (receive / receive_from first), and raises GgrsError(GGRS_E_STATE) otherwise -- where
+    SchedDesyncDetector would deliver those reports late."""
+
+    def __init__(self, engine, interval, addr=None, max_events=4096):
+        self.engine = engine
+        self.interval = interval
+        self.addr = addr
+        engine.set_desync_detection(interval)
+        engine.set_desync_compare(max_events)
+        self.max_events = max_events
+        self.remote_in = 0   # the peer's rows received so far
+        self.processed = 0   # calls compared
+        self.read = 0        # event records read
+        self.sent = 0
+
+    def note_arrivals(self, first_call, arrive_upto):
+        pass
+
+    def outgoing(self):
+        """The report rows of the calls run since the last outgoing(): (first_call, engine.reports)."""
+        current = self.engine.calls()
+        first, n = self.sent, current - self.sent
+        self.sent = current
+        return first, self.engine.reports(first, n) if n > 0 else None
+
+    def receive(self, first_call, rows):
+        """The remote peer's outgoing() rows (its calls first_call ..): numpy arrays or device tensors."""
+        if rows is None:
+            return
+        assert first_call == self.remote_in, "remote report rows must be received in order"
+        self.engine.add_remote_reports(first_call, rows["frame"], rows["checksum"], rows["local_last"])
+        self.remote_in += int(rows["frame"].shape[0])
+
+    def receive_from(self, peer_engine):
+        """The rows of every call `peer_engine` has run since the last one, device to device."""
+        n = peer_engine.calls() - self.remote_in
+        if n > 0:
+            self.engine.add_remote_reports_from(peer_engine, self.remote_in, n)
+            self.remote_in += n
+
+    def poll(self):
+        """Compare every call run so far on the device and return the DesyncDetected events raised
+        since the last poll, sorted by (call, session, frame) -- those the device's event list kept
+        (engine.desync_state() counts every one)."""
+        current = self.engine.calls()
+        if current <= self.processed:
+            return []
+        self.engine.compare_reports(self.processed, current - self.processed)
+        self.processed = current
+        call, session, frame, local, remote = self.engine.desync_events(self.read, self.max_events)
+        self.read += len(call)
+        events = [DesyncDetected(int(f), int(s), int(l), int(r), self.addr, int(c))
+                  for c, s, f, l, r in zip(call, session, frame, local, remote)]
+        events.sort(key=lambda ev: (ev.call, ev.session, ev.frame))
+        return events

@@ -82,6 +82,12 @@ def _bind(L):
     L.ggrs_p2p_set_time_sync.argtypes = [vp, i32]
     L.ggrs_p2p_time_sync.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32]
     L.ggrs_p2p_read_time_sync_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.ggrs_p2p_set_desync_compare.argtypes = [vp, i32]
+    L.ggrs_p2p_add_remote_reports.argtypes = [vp, i32, i32, vp, vp, vp, i32]
+    L.ggrs_p2p_add_remote_reports_from.argtypes = [vp, vp, i32, i32]
+    L.ggrs_p2p_compare_reports.argtypes = [vp, i32, i32, P(i32)]
+    L.ggrs_p2p_read_desync_events.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, P(i32)]
+    L.ggrs_p2p_read_desync_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in _lib.EXPORTS:
         if name.startswith("ggrs_p2p_"):
             getattr(L, name).restype = ctypes.c_int
@@ -440,6 +446,56 @@ class P2PEngine:
         S = self.num_sessions
         out = [np.zeros(S, np.int32) for _ in range(5)] + [np.zeros((2, 30, S), np.int32)]
         _lib.check(self._L.ggrs_p2p_read_time_sync_state(self._h, *(_vp(a) for a in out)))
+        return tuple(out)
+
+    # ---- checksum comparison (include/ggrs_amd.h, ggrs_p2p_*desync_compare/reports*; p2p_desync.hip)
+    def set_desync_compare(self, max_events=4096):
+        """The peer's checksum reports are kept and compared on the device (add_remote_reports,
+        compare_reports); after set_arrival_schedule and set_desync_detection(interval > 0), before the
+        first call.  max_events: the records of the device's event list."""
+        _lib.check(self._L.ggrs_p2p_set_desync_compare(self._h, max_events))
+        self.max_desync_events = max_events
+
+    def add_remote_reports(self, first_call, frames, checksums, local_last):
+        """The peer's reports() rows of its calls first_call .. (in call order from 0): frame [n][S]
+        int32, checksum [n][S] uint16 and local_last [n][S] int32 -- numpy arrays, or torch tensors on
+        the engine's device (checksum int16 or uint16), copied on the engine's stream."""
+        n, S = int(frames.shape[0]), self.num_sessions
+        dev = hasattr(frames, "data_ptr")
+        ck = "uint16"
+        if dev and str(checksums.dtype) == "torch.int16":
+            ck = "int16"  # (the bits of the u16 values)
+        ptrs, keep = _lib.marshal((frames, checksums, local_last), ((n, S),) * 3, ("int32", ck, "int32"), dev)
+        _lib.check(self._L.ggrs_p2p_add_remote_reports(self._h, first_call, n, *ptrs, int(dev)))
+
+    def add_remote_reports_from(self, peer, first_call, n_calls):
+        """The same rows straight from the P2PEngine `peer`'s report rows, device to device."""
+        _lib.check(self._L.ggrs_p2p_add_remote_reports_from(self._h, peer._h, first_call, n_calls))
+
+    def compare_reports(self, first_call, n_calls, wait=True):
+        """Delivery, the local report and the comparison of calls first_call .. first_call + n_calls - 1
+        (already run, in order, each once; the peer's rows through call first_call + n_calls - 2 added).
+        Returns the events raised so far in all (wait=False: None, without waiting for the launch)."""
+        total = ctypes.c_int32()
+        _lib.check(self._L.ggrs_p2p_compare_reports(self._h, first_call, n_calls, ctypes.byref(total) if wait else None))
+        return total.value if wait else None
+
+    def desync_events(self, first=0, max_records=None):
+        """Records first .. of the device's event list: (call, session, frame [n] int32, local, remote
+        [n] uint16)."""
+        n = getattr(self, "max_desync_events", 0) if max_records is None else max_records
+        out = [np.zeros(n, np.int32) for _ in range(3)] + [np.zeros(n, np.uint16) for _ in range(2)]
+        got = ctypes.c_int32()
+        _lib.check(self._L.ggrs_p2p_read_desync_events(self._h, first, n, *(_vp(a) for a in out), ctypes.byref(got)))
+        return tuple(a[:got.value] for a in out)
+
+    def desync_state(self):
+        """(status, n_events, first_call, first_frame, first_local, first_remote, refused) [S] int32
+        each and (history, pending) [2][32][S] int32: the tables' frames (-1 past the entries) then
+        their checksums."""
+        S = self.num_sessions
+        out = [np.zeros(S, np.int32) for _ in range(7)] + [np.zeros((2, 32, S), np.int32) for _ in range(2)]
+        _lib.check(self._L.ggrs_p2p_read_desync_state(self._h, *(_vp(a) for a in out)))
         return tuple(out)
 
     KERNEL_FORMS = {"default": 0, "unstaged": 1, "lockstep": 2, "flat": 3, "chains": 4, "flat_queues": 5,

@@ -599,7 +599,8 @@ int ggrs_p2p_read_sessions(ggrs_p2p_engine_t* eng, int32_t* frames, int32_t* ski
  * last_confirmed_frame compare_local_checksums_against_peers compared against in that call, and
  * the local players' last queued frame after the call (the reports travel with those inputs).
  * The pending-report bookkeeping and comparison are the caller's (ggrs_amd/desync.py
- * SchedDesyncDetector: UdpProtocol::on_checksum_report, protocol.rs:663-682).  A session whose
+ * SchedDesyncDetector: UdpProtocol::on_checksum_report, protocol.rs:663-682) unless
+ * ggrs_p2p_set_desync_compare hands them to the device (below).  A session whose
  * report cell is gone (the reference panics, :951-954) stops with GGRS_E_PRECONDITION.  Any output
  * pointer may be NULL. */
 int ggrs_p2p_read_reports(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, int32_t* frames,
@@ -839,6 +840,74 @@ int ggrs_p2p_time_sync(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_cal
 int ggrs_p2p_read_time_sync_state(ggrs_p2p_engine_t* eng, int32_t* local_advantage, int32_t* remote_advantage,
                                   int32_t* rtt_ms, int32_t* next_recommended_sleep, int32_t* closed_call,
                                   int32_t* windows);
+
+/* ---- Checksum comparison: the receive side of desync detection under arrival schedules, every
+ * session's GgrsEvent::DesyncDetected on the device: UdpProtocol::on_checksum_report
+ * (protocol.rs:663-682) and compare_local_checksums_against_peers (p2p_session.rs:904-937) with the
+ * history push of check_checksum_send_interval (:965-970), over the report rows the scheduled kernels
+ * store (ggrs_p2p_read_reports) and the peer's.  One endpoint per session holds all of its remote
+ * players, as in packet emit.  Arrival-schedule mode and ggrs_p2p_set_desync_detection(interval > 0) are
+ * required; lockstep mode (which sends no report), the packet feed, the emits and time sync combine with
+ * it.  Per session local_checksum_history and pending_checksums hold at most 32 (frame, u16 checksum)
+ * entries (MAX_CHECKSUM_HISTORY_SIZE, protocol.rs:27), both empty at first.  Call c, after it ran:
+ *  1. delivery: the peer's rows g = (rows delivered so far), .. while g < c and local_last of the peer's
+ *     row g (the inputs its report travelled with) <= last_recv_frame of call c -- the feed's ack_frame
+ *     with the packet feed, else the running maximum of the arrival rows.  A row with frame >= 0 is
+ *     on_checksum_report: with 32 reports pending those with frame < frame - 31 interval are dropped
+ *     first, then the report is inserted.  Divergence: a report whose frame is not a positive multiple of
+ *     the interval, or not above the newest frame received from the peer so far, is refused and counted
+ *     (the reference accepts any frame; a peer of the same configuration sends no such report), so the
+ *     table never exceeds 32 entries;
+ *  2. the call's own report (frame >= 0) enters the history; a 33rd entry prunes it to frames >=
+ *     frame - 31 interval;
+ *  3. every pending report, in ascending frame order (the reference iterates a HashMap), with frame <
+ *     the call's last_confirmed and its frame in the history is compared and removed; a difference is a
+ *     DesyncDetected: (call, session, frame, local checksum, remote checksum);
+ *  4. a session that stopped takes its rows as ggrs_p2p_read_reports returns them (no report).  A
+ *     session whose next row to deliver is more than input_capacity rows behind the rows added when
+ *     ggrs_p2p_compare_reports is called has lost that row to the ring: its status becomes
+ *     GGRS_DESYNC_ROW_LOST and it takes no step and raises nothing from that invocation's first call on;
+ *     the other sessions go on.
+ * Events go to a list of max_events records; the count stays exact when the list is full (which records
+ * a full list keeps is unspecified), and so does the per-session summary.  Not built: the ChecksumReport
+ * message envelope, several endpoints per session, fixed-latency engines (ggrs_p2p_compare_checksums).
+ * The scheduled kernels store nothing new.  Kernel: p2p_desync.hip. */
+#define GGRS_DESYNC_ROW_LOST (-21)  /* a peer's report row was overwritten before the session read it */
+/* Part of the configuration (after ggrs_p2p_set_arrival_schedule(eng, 1) and
+ * ggrs_p2p_set_desync_detection(eng, interval > 0), before the first call): max_events in 1..2^26
+ * (GGRS_E_INVALID otherwise).  GGRS_E_STATE after the first call, on a fixed-latency engine and without
+ * desync detection. */
+int ggrs_p2p_set_desync_compare(ggrs_p2p_engine_t* eng, int32_t max_events);
+/* The peer's ggrs_p2p_read_reports rows (frames, checksums, local_last; [n][S] each) of its calls
+ * first_call .. first_call + n_calls - 1: in call order from 0, n_calls <= input_capacity (GGRS_E_INVALID
+ * otherwise).  on_device != 0: device pointers, copied on the engine's stream.  The engine keeps the last
+ * input_capacity rows. */
+int ggrs_p2p_add_remote_reports(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, const int32_t* frames,
+                                const uint16_t* checksums, const int32_t* local_last, int32_t on_device);
+/* The same rows straight from the peer engine's report rows, device to device: calls the peer has run
+ * that are among its last input_capacity (GGRS_E_INVALID otherwise); the same sessions on the same
+ * device.  The copy waits for the peer's launches and the peer's next launch for the copy. */
+int ggrs_p2p_add_remote_reports_from(ggrs_p2p_engine_t* eng, ggrs_p2p_engine_t* peer_eng, int32_t first_call,
+                                     int32_t n_calls);
+/* Steps 1-4 for calls first_call .. first_call + n_calls - 1: already run, in order, each exactly once,
+ * still among the last input_capacity calls (GGRS_E_INVALID otherwise).  GGRS_E_STATE, naming the
+ * missing call, unless the peer's rows through call first_call + n_calls - 2 were added: no report is
+ * ever delivered later than the reference delivers it.  n_events_total (may be NULL: then the call does
+ * not wait for the launch): the events raised so far, by every invocation.  The events and the state do
+ * not depend on how the calls are split over invocations (GGRS_DESYNC_ROW_LOST does: it is found where
+ * an invocation starts). */
+int ggrs_p2p_compare_reports(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, int32_t* n_events_total);
+/* Records first .. first + max - 1 of the event list, in the order they were appended (unspecified
+ * within an invocation): n_read of them (at most max_events exist).  Any array may be NULL. */
+int ggrs_p2p_read_desync_events(ggrs_p2p_engine_t* eng, int32_t first, int32_t max, int32_t* call, int32_t* session,
+                                int32_t* frame, uint16_t* local, uint16_t* remote, int32_t* n_read);
+/* Per session, [num_sessions] each: status (0, GGRS_DESYNC_ROW_LOST), the events raised, the first
+ * event's call (-1: none), frame (-1), local and remote checksum, the reports refused; history and
+ * pending [2][32][S] each: the entries' frames in ascending order (-1 past the last), then their
+ * checksums (0).  Any pointer may be NULL. */
+int ggrs_p2p_read_desync_state(ggrs_p2p_engine_t* eng, int32_t* status, int32_t* n_events, int32_t* first_call,
+                               int32_t* first_frame, int32_t* first_local, int32_t* first_remote, int32_t* refused,
+                               int32_t* history, int32_t* pending);
 
 /* ---------------------------------------------------------------------------------------------
  * Spectators: num_sessions independent SpectatorSessions (src/sessions/p2p_spectator_session.rs),

@@ -33,6 +33,7 @@ const UNITS: &[(&str, &[&str])] = &[
     ("spectator_ingest.hip", NONE),
     ("p2p_spec_emit.hip", NONE),
     ("p2p_time_sync.hip", NONE),
+    ("p2p_desync.hip", NONE),
 ];
 
 fn main() {

@@ -57,6 +57,7 @@ pub const GGRS_EMIT_CLOSED: i32 = -18;
 pub const GGRS_EMIT_DISCONNECTED: i32 = -19;
 pub const GGRS_EMIT_ROW_LOST: i32 = -20;
 pub const GGRS_TIME_SYNC_KEEP: i32 = i32::MIN;
+pub const GGRS_DESYNC_ROW_LOST: i32 = -21;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -417,6 +418,48 @@ extern "C" {
         next_recommended_sleep: *mut i32,
         closed_call: *mut i32,
         windows: *mut i32,
+    ) -> i32;
+    // checksum comparison (p2p_desync.hip): on_checksum_report and DesyncDetected per call, on the device
+    pub fn ggrs_p2p_set_desync_compare(eng: *mut ggrs_p2p_engine_t, max_events: i32) -> i32;
+    pub fn ggrs_p2p_add_remote_reports(
+        eng: *mut ggrs_p2p_engine_t,
+        first_call: i32,
+        n_calls: i32,
+        frames: *const i32,
+        checksums: *const u16,
+        local_last: *const i32,
+        on_device: i32,
+    ) -> i32;
+    pub fn ggrs_p2p_add_remote_reports_from(
+        eng: *mut ggrs_p2p_engine_t,
+        peer_eng: *mut ggrs_p2p_engine_t,
+        first_call: i32,
+        n_calls: i32,
+    ) -> i32;
+    pub fn ggrs_p2p_compare_reports(eng: *mut ggrs_p2p_engine_t, first_call: i32, n_calls: i32,
+                                    n_events_total: *mut i32) -> i32;
+    pub fn ggrs_p2p_read_desync_events(
+        eng: *mut ggrs_p2p_engine_t,
+        first: i32,
+        max: i32,
+        call: *mut i32,
+        session: *mut i32,
+        frame: *mut i32,
+        local: *mut u16,
+        remote: *mut u16,
+        n_read: *mut i32,
+    ) -> i32;
+    pub fn ggrs_p2p_read_desync_state(
+        eng: *mut ggrs_p2p_engine_t,
+        status: *mut i32,
+        n_events: *mut i32,
+        first_call: *mut i32,
+        first_frame: *mut i32,
+        first_local: *mut i32,
+        first_remote: *mut i32,
+        refused: *mut i32,
+        history: *mut i32,
+        pending: *mut i32,
     ) -> i32;
 
     // ---- spectators (src/sessions/p2p_spectator_session.rs), batched
