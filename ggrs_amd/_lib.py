@@ -26,6 +26,8 @@ GGRS_EMIT_CLOSED, GGRS_EMIT_DISCONNECTED = -18, -19  # ggrs_p2p_read_emit_state'
 GGRS_EMIT_ROW_LOST = -20  # ggrs_p2p_read_spectator_emit_state's own status
 GGRS_TIME_SYNC_KEEP = -2 ** 31  # ggrs_p2p_time_sync's remote_advantage: no report at this call
 GGRS_DESYNC_ROW_LOST = -21  # ggrs_p2p_read_desync_state's status
+# ggrs_wire_unpack's slot_status codes (accepted: tag + 1, empty: 0)
+GGRS_WIRE_E_BINCODE, GGRS_WIRE_E_SHAPE, GGRS_WIRE_E_CAP, GGRS_WIRE_E_CLOCK, GGRS_WIRE_E_RANGE = -22, -23, -24, -25, -26
 NULL_FRAME = -1
 REQ_SAVE, REQ_LOAD, REQ_ADVANCE = 0, 1, 2
 STATUS_CONFIRMED, STATUS_PREDICTED, STATUS_DISCONNECTED = 0, 1, 2
@@ -78,6 +80,7 @@ EXPORTS = (
     "ggrs_spectator_timing_reset", "ggrs_spectator_timing_stop", "ggrs_spectator_timing_read",
     "ggrs_spectator_set_packet_feed", "ggrs_spectator_receive_packets", "ggrs_spectator_read_packet_results",
     "ggrs_codec_encode", "ggrs_codec_decode", "ggrs_codec_encode_chunked", "ggrs_codec_decode_chunked", "ggrs_codec_max_packet_bytes", "ggrs_codec_set_direct",
+    "ggrs_wire_max_datagram_bytes", "ggrs_wire_unpack", "ggrs_wire_pack",
 )
 
 
@@ -182,7 +185,8 @@ def lib():
         L.ggrs_read_lane_frames.argtypes = [vp, vp]
         L.ggrs_lane_server.argtypes = [vp, i32]
         for name in EXPORTS:
-            if name not in ("ggrs_abi_version", "ggrs_last_error", "ggrs_codec_max_packet_bytes"):
+            if name not in ("ggrs_abi_version", "ggrs_last_error", "ggrs_codec_max_packet_bytes",
+                            "ggrs_wire_max_datagram_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         _lib = L
     return _lib

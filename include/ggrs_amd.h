@@ -613,9 +613,9 @@ int ggrs_p2p_read_reports(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_
  * c; the remote players' columns are ignored and hold arbitrary bytes until their packet arrives) ->
  * ggrs_p2p_receive_packets -> ggrs_p2p_advance_frames.  One packet carries one byte per remote player
  * per frame, ascending player order (InputBytes::to_player_inputs over the endpoint's handles); all
- * remote players of a session share one arrival stream, as in the arrival schedules.  The host still
- * parses the Input message envelope (start_frame; ack_frame for its own send side; connect status ->
- * ggrs_p2p_add_peer_reports; disconnect_requested -> events).
+ * remote players of a session share one arrival stream, as in the arrival schedules.  ggrs_wire_unpack
+ * (or the host) parses the Input message envelope (start_frame; ack_frame for its own send side; connect
+ * status -> ggrs_p2p_add_peer_reports; disconnect_requested -> events).
  * Per session last_recv_frame starts at GGRS_NULL_FRAME; a packet (start, bytes) at call c:
  *  1. last_recv != NULL && last_recv + 1 < start is the reference's assert! (:588-590), and so is a
  *     first packet with start != 0: the session stops at call c with GGRS_E_PRECONDITION;
@@ -686,7 +686,7 @@ int ggrs_p2p_read_packet_results(ggrs_p2p_engine_t* eng, int32_t first_call, int
  *  5. ack_frame[c] = the endpoint's last_recv_frame after call c (the packet feed's, or the newest frame
  *     of the arrival rows), written for every call: what the Input message or a bare InputAck carries;
  *  6. a session that stopped (an error in ggrs_p2p_read_sessions) emits nothing from its stopping call on.
- * The host still fills the envelope: peer_connect_status and disconnect_requested.  With emit
+ * ggrs_wire_pack (or the host) fills the envelope: peer_connect_status and disconnect_requested.  With emit
  * configured the scheduled kernels store one more word per session and call.  Kernel: p2p_emit.hip. */
 #define GGRS_EMIT_CLOSED (-18)        /* the stream closed on an Event::Disconnected of a remote player */
 #define GGRS_EMIT_DISCONNECTED (-19)  /* more than max_pending_inputs unacknowledged inputs */
@@ -752,8 +752,8 @@ int ggrs_p2p_read_emit_state(ggrs_p2p_engine_t* eng, int32_t* last_acked, int32_
  *     on: the emit was called too late for this input_capacity.  Emitting call c needs the rows from
  *     next_spectator_frame on, so emit before more than input_capacity - (the longest arrival stall in
  *     calls) - 1 further rows are added.
- * The Input envelope's ack_frame and disconnect_requested stay with the host (a spectator sends no
- * inputs).  The scheduled kernels store what they store for packet emit, one word per session and
+ * The Input envelope's ack_frame and disconnect_requested are ggrs_wire_pack's or the host's (a spectator
+ * sends no inputs).  The scheduled kernels store what they store for packet emit, one word per session and
  * call; confirmed_frame and the connect status are restated by the emit from that word, the arrival
  * rows and the events.  Kernel: p2p_spec_emit.hip. */
 #define GGRS_EMIT_ROW_LOST (-20)  /* an input row to push was overwritten before the emit read it */
@@ -816,8 +816,8 @@ int ggrs_p2p_read_spectator_emit_state(ggrs_p2p_engine_t* eng, int32_t* next_spe
  *  7. local_advantage[c] = local_frame_advantage after the call: NetworkStats::local_frames_behind, and
  *     what a QualityReport sent at this call carries.
  * Not built: the recommendation is reported, not enacted (every session of an engine takes every call);
- * the QualityReport / QualityReply messages, their 200 ms timer and the rest of the envelope stay with
- * the host, as do NetworkStats' send_queue_len and kbps_sent; fixed-latency engines and peer reports.
+ * the QualityReport / QualityReply messages are ggrs_wire_unpack's and ggrs_wire_pack's, their 200 ms
+ * timer stays with the host, as do NetworkStats' send_queue_len and kbps_sent; fixed-latency engines and peer reports.
  * The scheduled kernels store what they store for packet emit, one word per session and call.
  * Kernel: p2p_time_sync.hip. */
 #define GGRS_TIME_SYNC_KEEP INT32_MIN /* remote_advantage: no QualityReport arrived at this call */
@@ -869,8 +869,8 @@ int ggrs_p2p_read_time_sync_state(ggrs_p2p_engine_t* eng, int32_t* local_advanta
  *     GGRS_DESYNC_ROW_LOST and it takes no step and raises nothing from that invocation's first call on;
  *     the other sessions go on.
  * Events go to a list of max_events records; the count stays exact when the list is full (which records
- * a full list keeps is unspecified), and so does the per-session summary.  Not built: the ChecksumReport
- * message envelope, several endpoints per session, fixed-latency engines (ggrs_p2p_compare_checksums).
+ * a full list keeps is unspecified), and so does the per-session summary.  The ChecksumReport message
+ * envelope is ggrs_wire_unpack's and ggrs_wire_pack's.  Not built: several endpoints per session, fixed-latency engines (ggrs_p2p_compare_checksums).
  * The scheduled kernels store nothing new.  Kernel: p2p_desync.hip. */
 #define GGRS_DESYNC_ROW_LOST (-21)  /* a peer's report row was overwritten before the session read it */
 /* Part of the configuration (after ggrs_p2p_set_arrival_schedule(eng, 1) and
@@ -1034,8 +1034,8 @@ int ggrs_spectator_set_packet_feed(ggrs_spectator_engine_t* eng, int32_t max_pre
  * start_frame [n_calls][num_sessions] i32 (< 0: no packet), packet_len [n_calls][num_sessions] i32,
  * packets [n_calls][num_sessions][packet_stride] u8, one packet input = num_players bytes in player
  * order (InputBytes::from_inputs, protocol.rs:52-80); notes [n_calls][num_sessions] i32
- * (GGRS_SPECTATOR_NOTE or 0; NULL: none) -- the envelope's peer_connect_status, which the host still
- * parses.  A malformed note in host memory is GGRS_E_INVALID; with on_device the five pointers are
+ * (GGRS_SPECTATOR_NOTE or 0; NULL: none) -- the envelope's peer_connect_status, which ggrs_wire_unpack
+ * writes as its notes.  A malformed note in host memory is GGRS_E_INVALID; with on_device the five pointers are
  * device memory (packets dword aligned) read by a launch on the engine's stream, and a malformed
  * note counts as none.  GGRS_E_STATE without ggrs_spectator_set_packet_feed. */
 int ggrs_spectator_receive_packets(ggrs_spectator_engine_t* eng, int32_t first_call, int32_t n_calls,
@@ -1096,6 +1096,119 @@ int32_t ggrs_codec_max_packet_bytes(int32_t input_bytes, int32_t max_inputs);
  * rows are whole dwords, else direct), 1 = direct thread-per-packet, 2 = thread-per-packet
  * LDS-staged where it applies */
 int ggrs_codec_set_direct(int32_t mode);
+
+/* ---- Wire envelope, batched (kernel: wire.hip): what a socket hands a GGRS host is a datagram,
+ * bincode::serialize(&Message) (src/network/udp_socket.rs, src/network/messages.rs:5-129).  Unpack turns
+ * the raw datagrams of a poll into the dense arrays the P2P and spectator units take -- UdpProtocol::
+ * handle_message (src/network/protocol.rs:534-562), on_input's envelope part (:564-585), on_input_ack,
+ * on_quality_report and on_quality_reply (:644-660) -- and pack turns the units' output arrays into
+ * datagrams (queue_message :515-528 over the bodies of :450-513 and :692-698), so two engines play each
+ * other datagram to datagram in the bytes a GGRS 0.10.2 peer sends and accepts.  Stateless like the
+ * codec: all pointers are DEVICE pointers, `stream` is a hipStream_t (NULL: default).
+ * Layout (bincode 1.3: fixed-width little-endian integers, u32 enum tag, u64 Vec length, a bool as one
+ * byte that must be 0 or 1, u128 as 16 bytes, declaration order, trailing bytes accepted):
+ *   Message            = magic u16 | tag u32 | body
+ *   Input (0)          = n u64 | n x (disconnected u8, last_frame i32) | disconnect_requested u8
+ *                        | start_frame i32 | ack_frame i32 | len u64 | bytes[len]   (31 + 5 n + len bytes)
+ *   InputAck (1)       = ack_frame i32                                            (10)
+ *   QualityReport (2)  = frame_advantage i16 | ping u128                          (24)
+ *   QualityReply (3)   = pong u128                                                (22)
+ *   ChecksumReport (4) = checksum u128 | frame i32                                (26)
+ *   KeepAlive (5)      = nothing                                                  (6)
+ * handle_message never checks the magic (0.10.2 has no sync handshake): unpack ignores it, pack writes
+ * the endpoint's.  What stays with the host: the sockets, the 200 ms timers (which calls set resend,
+ * send_report and keep_alive), NetworkStats' send_queue_len and kbps_sent, NetworkInterrupted /
+ * NetworkResumed and the disconnect timeouts. */
+#define GGRS_WIRE_INPUT 0
+#define GGRS_WIRE_INPUT_ACK 1
+#define GGRS_WIRE_QUALITY_REPORT 2
+#define GGRS_WIRE_QUALITY_REPLY 3
+#define GGRS_WIRE_CHECKSUM_REPORT 4
+#define GGRS_WIRE_KEEP_ALIVE 5
+/* slot_status: tag + 1 (1..6) = accepted, 0 = empty slot, else why the datagram was dropped whole: */
+#define GGRS_WIRE_E_BINCODE (-22) /* bincode::deserialize fails: short buffer, tag > 5, a bool byte > 1, a Vec
+                                     length that does not fit the datagram, a length beyond dgram_stride */
+#define GGRS_WIRE_E_SHAPE (-23)   /* an Input with fewer than num_statuses connect statuses: the reference indexes
+                                     past the end and panics (:577-578); extra entries are ignored as it ignores them */
+#define GGRS_WIRE_E_CAP (-24)     /* an Input whose bytes are longer than packet_stride */
+#define GGRS_WIRE_E_CLOCK (-25)   /* a QualityReply whose pong exceeds now_ms or has any of its upper 64 bits set:
+                                     the reference's assert! (:658) */
+#define GGRS_WIRE_E_RANGE (-26)   /* a ChecksumReport whose checksum does not fit the engine's 16 bits (a peer
+                                     running this game sends Fletcher-16 widened to u128): stated divergence,
+                                     counted, never silently truncated */
+/* 31 + 5 num_statuses + body_bytes rounded up to a multiple of 16: a dgram_stride every Input message of
+ * num_statuses statuses and body_bytes bytes fits */
+int32_t ggrs_wire_max_datagram_bytes(int32_t num_statuses, int32_t body_bytes);
+/* n_calls polls of num_sessions (S) endpoints, `slots` (M, 1..8) datagram slots per poll; num_statuses
+ * 1..4 (the session's players); remote_mask the events bits a disconnect request sets; first_call >= 0
+ * the call of row 0 (it rotates notes).  Inputs: dgrams [n][M][S][dgram_stride] u8 (dword aligned,
+ * dgram_stride a multiple of 4 in 8..2048), dgram_len [n][M][S] i32 (<= 0: empty; > dgram_stride:
+ * GGRS_WIRE_E_BINCODE), now_ms [n] u64 (the host's millis_since_epoch at each poll); packet_stride a
+ * multiple of 4 in 4..1012.  Outputs, [n][S] unless noted, any may be NULL; the slots of one (call,
+ * session) are folded in slot order, as handle_message would be called on them, a dropped datagram
+ * changing nothing:
+ *   slot_status [n][M][S] i32;
+ *   start_frame i32, packet_len i32, packets [n][S][packet_stride] u8 (dword aligned): the arrays
+ *     ggrs_p2p_receive_packets and ggrs_spectator_receive_packets read, holding the accepted Input with
+ *     the greatest start_frame, ties to the later slot; -1 / 0 without one.  A sender's start_frame is
+ *     its first unacknowledged frame, which never decreases, and it learned start_frame - 1 from an ack
+ *     this receiver sent, so that packet alone delivers every frame the fold over all of them would.
+ *     Stated divergence: two equal-start_frame packets arriving in reversed order lose the longer one's
+ *     tail until the next resend.  Bytes past packet_len are unspecified;
+ *   ack_in i32: the maximum of every accepted Input's and InputAck's ack_frame (pop_pending_output is
+ *     monotone, so the maximum equals the fold), GGRS_NULL_FRAME without one;
+ *   events u8: remote_mask when an accepted Input has disconnect_requested, else 0;
+ *   disc_mask u8 and last_frame [n][num_statuses][S] i32: the sticky merge of :577-584 over the poll's
+ *     accepted Inputs with disconnect_requested == false (bits 0, last_frame GGRS_NULL_FRAME without
+ *     one); the host keeps merging across polls, or feeds ggrs_p2p_add_peer_reports from it;
+ *   notes i32: the same status as ggrs_spectator_receive_packets takes it: 0 when no bit is set, else
+ *     with m set bits GGRS_SPECTATOR_NOTE(player, last_frame) of the ((first_call + i) mod m)-th in
+ *     ascending player order, the rule of ggrs_p2p_emit_spectator_packets' notes;
+ *   remote_advantage i32: the last accepted QualityReport's frame_advantage, sign-extended, else
+ *     GGRS_TIME_SYNC_KEEP; ping [n][S][16] u8 (dword aligned): that report's ping, verbatim, for the
+ *     reply (zeros without one).  Stated divergence: several reports of one poll get one reply, to the last;
+ *   rtt_ms i32: now_ms[i] - pong of the last accepted QualityReply, saturated at INT32_MAX
+ *     (ggrs_p2p_time_sync clamps further), -1 without one;
+ *   report_frame i32 and report_checksum u16: the accepted ChecksumReport with the greatest frame (ties
+ *     to the later slot), else GGRS_NULL_FRAME and 0.  Stated divergence: a poll keeps one report, the
+ *     older ones of a burst are dropped (their slot_status still counts them);
+ *   kinds u8: bit t set when a message of tag t was accepted.
+ * Never faults on hostile bytes; every output of a (call, session) is written whole, whatever the
+ * datagrams hold.  Bad arguments: GGRS_E_INVALID, nothing launched. */
+int ggrs_wire_unpack(int32_t n_calls, int32_t num_sessions, int32_t slots, int32_t num_statuses, uint32_t remote_mask,
+                     int32_t first_call, const uint8_t* dgrams, int32_t dgram_stride, const int32_t* dgram_len,
+                     const uint64_t* now_ms, int32_t packet_stride, int32_t* slot_status, int32_t* start_frame,
+                     int32_t* packet_len, uint8_t* packets, int32_t* ack_in, uint8_t* events, uint8_t* disc_mask,
+                     int32_t* last_frame, int32_t* notes, int32_t* remote_advantage, uint8_t* ping, int32_t* rtt_ms,
+                     int32_t* report_frame, uint16_t* report_checksum, uint8_t* kinds, void* stream);
+/* The units' output arrays of n_calls calls -> dgrams [n][4][S][dgram_stride] and dgram_len [n][4][S]:
+ * unpack's input layout with M = 4, so one engine's output is its peer's input through index arithmetic
+ * alone.  magic [S] u16 and now_ms [n] u64 are required; every other input is [n][S] unless noted and
+ * may be NULL (absent): start_frame, packet_len, ack_frame, packets [n][S][packet_stride] as
+ * ggrs_p2p_emit_packets writes them; disc_mask u8, last_frame [n][num_statuses][S] and
+ * disconnect_requested u8 for the Input envelope (absent: connected, GGRS_NULL_FRAME, false); send_ack
+ * u8; send_report u8 and local_advantage of ggrs_p2p_time_sync; kinds u8 and ping [n][S][16] as unpack
+ * wrote them; report_frame and report_checksum u16; keep_alive u8.  Fixed slots, an empty one has
+ * length 0:
+ *   0  Input{num_statuses statuses, disconnect_requested, start_frame, ack_frame, the packet's bytes} when
+ *      start_frame, packet_len and packets are present, start_frame >= 0 and 0 < packet_len <=
+ *      packet_stride; else InputAck{ack_frame} when send_ack; else KeepAlive when keep_alive and slots
+ *      1-3 are empty too (an absent ack_frame is GGRS_NULL_FRAME);
+ *   1  QualityReport{local_advantage clamped to i16, ping = now_ms} when send_report;
+ *   2  QualityReply{pong = ping} when kinds has the QualityReport bit;
+ *   3  ChecksumReport{checksum as u128, frame} when report_frame >= 0.
+ * dgram_stride: a multiple of 4, >= ggrs_wire_max_datagram_bytes(num_statuses, packet_stride), <= 2048
+ * (GGRS_E_INVALID otherwise, nothing launched).  Bytes past a datagram's length are unspecified.
+ * Routing checksum reports to the compare unit: a report unpacked at poll c goes into
+ * ggrs_p2p_add_remote_reports row c - 1 with local_last = GGRS_NULL_FRAME; ggrs_p2p_compare_reports(c)
+ * then delivers it in call c, where the reference's poll_remote_clients would. */
+int ggrs_wire_pack(int32_t n_calls, int32_t num_sessions, int32_t num_statuses, const uint16_t* magic,
+                   const uint64_t* now_ms, const int32_t* start_frame, const int32_t* packet_len,
+                   const int32_t* ack_frame, const uint8_t* packets, int32_t packet_stride, const uint8_t* disc_mask,
+                   const int32_t* last_frame, const uint8_t* disconnect_requested, const uint8_t* send_ack,
+                   const uint8_t* send_report, const int32_t* local_advantage, const uint8_t* kinds, const uint8_t* ping,
+                   const int32_t* report_frame, const uint16_t* report_checksum, const uint8_t* keep_alive,
+                   uint8_t* dgrams, int32_t dgram_stride, int32_t* dgram_len, void* stream);
 
 #ifdef __cplusplus
 }

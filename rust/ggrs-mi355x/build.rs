@@ -34,6 +34,7 @@ const UNITS: &[(&str, &[&str])] = &[
     ("p2p_spec_emit.hip", NONE),
     ("p2p_time_sync.hip", NONE),
     ("p2p_desync.hip", NONE),
+    ("wire.hip", NONE),
 ];
 
 fn main() {

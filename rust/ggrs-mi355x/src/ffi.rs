@@ -58,6 +58,18 @@ pub const GGRS_EMIT_DISCONNECTED: i32 = -19;
 pub const GGRS_EMIT_ROW_LOST: i32 = -20;
 pub const GGRS_TIME_SYNC_KEEP: i32 = i32::MIN;
 pub const GGRS_DESYNC_ROW_LOST: i32 = -21;
+// wire envelope: message tags and ggrs_wire_unpack's slot_status codes (accepted: tag + 1, empty: 0)
+pub const GGRS_WIRE_INPUT: i32 = 0;
+pub const GGRS_WIRE_INPUT_ACK: i32 = 1;
+pub const GGRS_WIRE_QUALITY_REPORT: i32 = 2;
+pub const GGRS_WIRE_QUALITY_REPLY: i32 = 3;
+pub const GGRS_WIRE_CHECKSUM_REPORT: i32 = 4;
+pub const GGRS_WIRE_KEEP_ALIVE: i32 = 5;
+pub const GGRS_WIRE_E_BINCODE: i32 = -22;
+pub const GGRS_WIRE_E_SHAPE: i32 = -23;
+pub const GGRS_WIRE_E_CAP: i32 = -24;
+pub const GGRS_WIRE_E_CLOCK: i32 = -25;
+pub const GGRS_WIRE_E_RANGE: i32 = -26;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -506,6 +518,23 @@ extern "C" {
                                      count: *mut i32, status: *mut i32, stream: *mut c_void) -> i32;
     pub fn ggrs_codec_max_packet_bytes(input_bytes: i32, max_inputs: i32) -> i32;
     pub fn ggrs_codec_set_direct(mode: i32) -> i32;
+
+    // ---- wire envelope, batched (wire.hip): bincode Message datagrams <-> the units' arrays; device pointers
+    pub fn ggrs_wire_max_datagram_bytes(num_statuses: i32, body_bytes: i32) -> i32;
+    pub fn ggrs_wire_unpack(n_calls: i32, num_sessions: i32, slots: i32, num_statuses: i32, remote_mask: u32,
+                            first_call: i32, dgrams: *const u8, dgram_stride: i32, dgram_len: *const i32,
+                            now_ms: *const u64, packet_stride: i32, slot_status: *mut i32, start_frame: *mut i32,
+                            packet_len: *mut i32, packets: *mut u8, ack_in: *mut i32, events: *mut u8,
+                            disc_mask: *mut u8, last_frame: *mut i32, notes: *mut i32, remote_advantage: *mut i32,
+                            ping: *mut u8, rtt_ms: *mut i32, report_frame: *mut i32, report_checksum: *mut u16,
+                            kinds: *mut u8, stream: *mut c_void) -> i32;
+    pub fn ggrs_wire_pack(n_calls: i32, num_sessions: i32, num_statuses: i32, magic: *const u16, now_ms: *const u64,
+                          start_frame: *const i32, packet_len: *const i32, ack_frame: *const i32, packets: *const u8,
+                          packet_stride: i32, disc_mask: *const u8, last_frame: *const i32,
+                          disconnect_requested: *const u8, send_ack: *const u8, send_report: *const u8,
+                          local_advantage: *const i32, kinds: *const u8, ping: *const u8, report_frame: *const i32,
+                          report_checksum: *const u16, keep_alive: *const u8, dgrams: *mut u8, dgram_stride: i32,
+                          dgram_len: *mut i32, stream: *mut c_void) -> i32;
 }
 
 /// The engine's last error message on this thread.
