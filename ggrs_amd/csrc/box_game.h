@@ -235,8 +235,9 @@ __device__ inline void advance_player_lean_sc(float& x, float& y, float& vx, flo
 }
 
 // One player's input decoded for advance_player_rec: everything the step derives from Input.inp
-// (ex_game.rs:283-309), computed once per (frame, session, player) when the input is staged and
-// shared by every chain that replays the frame (the v5 SyncTest kernel replays each frame 9 times).
+// (ex_game.rs:283-309), shared by every chain that replays the frame (the v5 SyncTest kernel
+// replays each frame 9 times and looks its records up in a 16-entry table; the P2P chains kernel
+// computes one per (frame, session, player) when the input is staged).
 //   delta: the turn's f32 addend (-RS, +RS) or +0.0 without a turn;
 //   thr:   the wrap threshold, 2pi with a turn, +inf without (a non-turning rot of exactly 2pi must
 //          stay 2pi: ex_game only applies rem_euclid when it turns);
@@ -246,17 +247,30 @@ __device__ inline void advance_player_lean_sc(float& x, float& y, float& vx, flo
 struct InputRec {
   uint32_t delta, thr, sgn, keep;
 };
-__host__ __device__ inline InputRec make_input_rec(uint32_t input) {
+__host__ __device__ constexpr InputRec make_input_rec(uint32_t input) {
   const uint32_t ud = input & (kInputUp | kInputDown), lr = input & (kInputLeft | kInputRight);
   const bool thrust = ud == kInputUp, brake = ud == kInputDown;
   const bool ccw = lr == kInputLeft, cw = lr == kInputRight;
-  InputRec r;
+  InputRec r{};
   r.delta = ccw ? __builtin_bit_cast(uint32_t, -kRotationSpeed) : (cw ? __builtin_bit_cast(uint32_t, kRotationSpeed) : 0u);
   r.thr = (ccw || cw) ? __builtin_bit_cast(uint32_t, kTwoPi) : 0x7f800000u;
   r.sgn = thrust ? 0u : 0x80000000u;
   r.keep = (thrust || brake) ? 0xffffffffu : 0u;
   return r;
 }
+// The record depends on the byte's four direction bits only, so a table of kInputRecMask + 1
+// records indexed by (byte & kInputRecMask) is make_input_rec of every byte (the v5 SyncTest
+// kernel's lds_tab).  Checked for all 256 bytes, field for field.
+constexpr uint32_t kInputRecMask = kInputUp | kInputDown | kInputLeft | kInputRight;
+constexpr bool input_rec_reads_masked_bits_only() {
+  for (uint32_t b = 0; b < 256u; ++b) {
+    const InputRec a = make_input_rec(b), m = make_input_rec(b & kInputRecMask);
+    if (a.delta != m.delta || a.thr != m.thr || a.sgn != m.sgn || a.keep != m.keep) return false;
+  }
+  return true;
+}
+static_assert(kInputRecMask == 15u, "the record table holds one entry per value of the low four bits");
+static_assert(input_rec_reads_masked_bits_only(), "make_input_rec(b) must equal make_input_rec(b & kInputRecMask)");
 
 // advance_player_lean_sc from a staged InputRec, with the same IEEE results:
 //   * velocity increment (thrust ? d : brake ? -d : -0.0f) as bit operations:

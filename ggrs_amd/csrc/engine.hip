@@ -633,21 +633,30 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   constexpr int kEntry = 32;        // stash bytes per (session, player): 5 fields, 16-B aligned
   constexpr int kSlot = 8 * kEntry; // one step's stash (ROW entries)
   // inputs: the raw bytes of up to kRaw frames (the whole launch at n <= kRaw - CD, read in the
-  // prologue beside every other global read: one memory latency per launch), and their decoded
-  // InputRec for kStage5 frames at a time (+1 slack row for the batch's look-ahead), decoded from
-  // LDS every kStage5 steps; the non-core steps read the raw bytes
-  // (the split kernel stages half as many rows at a time: with its hand-off buffers a block then
-  // holds 39 KB of LDS, and four blocks -- eight waves, two per SIMD -- still share a CU's 160 KB)
-  constexpr int kStage5 = kSplit ? 64 : 128;
+  // prologue beside every other global read: one memory latency per launch; +1 slack row, which
+  // the read-ahead past the launch's last row lands in).  The core, edge and batch steps take
+  // their InputRec from lds_tab, make_input_rec of the byte's low four bits (the only bits it
+  // reads: box_game.h checks that) -- 16 records, the same for every session, frame and launch,
+  // written once in the prologue: 256 bytes, each of the 64 banks once, and all roles of a
+  // (session, player) read the same entry.  The general steps use the raw byte itself.
+  // Every kHold steps the wave checks that the next kHold + 1 rows are held (hold_rows); kHold is
+  // only that grid, for both instantiations (rows are re-read on it, so lds_raw's row 0 is always
+  // a step on the grid).  The core loop reads one 8-step block and the batch's row ahead: at most
+  // rows t + 8 .. t + 16 of a block at step t.  Inside a checked window those are held rows or,
+  // past the launch's last row, row raw_rows at most; from the block before a grid step g they
+  // are rows g .. g + 8, and g - row 0 is a multiple of kHold below raw_rows <= kRaw.  So the
+  // largest index read is the slack row's, as long as:
+  constexpr int kHold = 64;
   constexpr int kRaw = 528;
-  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[kRaw * ROW];
-  __shared__ uint4 lds_rec[(kStage5 + 1) * ROW];
+  static_assert((kRaw - 1) / kHold * kHold + kB <= kRaw, "a block read ahead across a re-read must end inside lds_raw");
+  __shared__ __attribute__((aligned(16))) uint8_t lds_raw[(kRaw + 1) * ROW];
+  __shared__ uint4 lds_tab[kInputRecMask + 1];
   __shared__ uint16_t lds_first[CD * SPW];
   __shared__ __attribute__((aligned(16))) uint8_t lds_stash[2 * kB * kSlot];  // slots, then the dump
   // Split kernel: the producer wave's hand-off to the consumer wave, two buffers of one 8-step
   // block each.  A step's slot holds every lane's post-advance state (fields 0..3 as one uint4 per
   // lane, then field 4 as one word per lane); lds_hrec holds, per buffer and lane, the InputRec
-  // the lane's batch sub-step needs (lds_rec itself is restaged while the consumer still works).
+  // the lane's batch sub-step needs (lds_raw is re-read while the consumer still works).
   constexpr int kHSlot = kWave * 20;
   __shared__ __attribute__((aligned(16))) uint8_t lds_hand[kSplit ? 2 * kB * kHSlot : 16];
   __shared__ uint4 lds_hrec[kSplit ? 2 * kWave : 1];
@@ -806,6 +815,10 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
     const int gg = wl / nsess, ss = wl - gg * nsess;
     lds_first[gg * SPW + ss] = firstv;
   }
+  if (!consumer && wl <= (int)kInputRecMask) {
+    const InputRec r = make_input_rec((uint32_t)wl);
+    lds_tab[wl] = make_uint4(r.delta, r.thr, r.sgn, r.keep);
+  }
   int32_t raw0 = p.f0;  // step whose frame (raw0 - cd) is lds_raw's row 0
   if (fast) {
 #pragma unroll
@@ -816,7 +829,7 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   } else if (!consumer) {
     stage_input_rows<ROW>(lds_raw, p.inputs, L, Pp, p.cap, g0, nraw, s0, nsess * Pp, ROW, wl);
   }
-  // lds_raw, lds_rec, lds_first and lds_stash belong to one wave (the split kernel's producer): LDS
+  // lds_raw, lds_tab, lds_first and lds_stash belong to one wave (the split kernel's producer): LDS
   // written by one lane and read by another needs only the wave's own in-order LDS queue and a
   // compiler fence (a __syncthreads would also wait for the checkpoint's stores; inside the step
   // loop, for every ring store in flight)
@@ -841,27 +854,23 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   const int32_t ramp_end = min(p.f0 + CD, t_end);
   const bool lean_ok = __all(w[4] <= kTwoPiBits);
   const int32_t core_end = (corrupt_here || !lean_ok) ? ramp_end : max(ramp_end, p.f0 + p.n);
-  int32_t chunk0 = p.f0;  // step of lds_rec's row 0
 
-  // decode the records of steps t .. t + kStage5 (from lds_raw; a launch longer than the raw chunk
-  // re-reads its raw rows first, the only global read inside the step loop)
-  auto stage = [&](int32_t t) {
-    const int nf = (t_stage_end - t) < kStage5 + 1 ? (t_stage_end - t) : kStage5 + 1;
-    if (t - raw0 + nf > raw_rows) {
-      wave_lds_sync();
-      const int nr = (t_stage_end - t) < raw_rows ? (t_stage_end - t) : raw_rows;
-      stage_input_rows<ROW>(lds_raw, p.inputs, L, Pp, p.cap, t - CD, nr, s0, nsess * Pp, ROW, wl);
-      raw0 = t;
-    }
+  // the raw rows of steps t .. t + kHold are held: a launch longer than the raw chunk re-reads its
+  // rows from step t on, the only global read inside the step loop.  True if it did (records read
+  // ahead of the call are then stale).
+  auto hold_rows = [&](int32_t t) -> bool {
+    const int nf = (t_stage_end - t) < kHold + 1 ? (t_stage_end - t) : kHold + 1;
+    if (t - raw0 + nf <= raw_rows) return false;
     wave_lds_sync();
-    const uint8_t* src = lds_raw + (t - raw0) * ROW;
-    for (int q = wl; q < nf * ROW; q += kWave) {
-      const InputRec r = make_input_rec(src[q]);
-      lds_rec[q] = make_uint4(r.delta, r.thr, r.sgn, r.keep);
-    }
-    chunk0 = t;
+    const int nr = (t_stage_end - t) < raw_rows ? (t_stage_end - t) : raw_rows;
+    stage_input_rows<ROW>(lds_raw, p.inputs, L, Pp, p.cap, t - CD, nr, s0, nsess * Pp, ROW, wl);
+    raw0 = t;
     wave_lds_sync();
+    return true;
   };
+  auto on_hold_grid = [&](int32_t t) { return ((t - p.f0) & (kHold - 1)) == 0; };
+  // the InputRec of a raw input byte
+  auto tab_rec = [&](uint32_t raw) -> uint4 { return lds_tab[raw & kInputRecMask]; };
 
   uint32_t acc = 0;
   const uint32_t in_at = (uint32_t)in_lane;
@@ -1038,7 +1047,7 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
       v[4] = *reinterpret_cast<const uint32_t*>(st + 16);
     }
     if constexpr (kCore) {
-      batch_run(core_tag, tb, count, v, lds_rec[(uint32_t)(tb + (j & (kB - 1)) + 1 - chunk0) * ROW + in_at]);
+      batch_run(core_tag, tb, count, v, tab_rec(lds_raw[(uint32_t)(tb + (j & (kB - 1)) + 1 - raw0) * ROW + in_at]));
     } else {
       batch_run(core_tag, tb, count, v, lds_raw[(uint32_t)(tb + (j & (kB - 1)) + 1 - raw0) * ROW + in_at]);
     }
@@ -1047,7 +1056,7 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   auto input_at = [&](int32_t t) -> uint32_t { return lds_raw[(uint32_t)(t - raw0) * ROW + in_at]; };
   auto general = [&](int32_t t) {
     const int32_t rel = t - p.f0;
-    if ((rel & (kStage5 - 1)) == 0) stage(t);
+    if (on_hold_grid(t)) hold_rows(t);
     step(std::false_type(), t, input_at(t), (uint32_t)(rel & (kB - 1)) * kSlot);
     if ((rel & (kB - 1)) == kB - 1) batch(std::false_type(), t - (kB - 1), kB);
   };
@@ -1107,11 +1116,11 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   // others take the general step there
   const bool edge_ok = core_end == p.f0 + p.n && (p.n & (kB - 1)) == 0 && p.n >= 2 * kB;
   auto edge_block = [&](int32_t tb, int count) {
-    if (((tb - p.f0) & (kStage5 - 1)) == 0 || tb + count + 1 > chunk0 + kStage5 + 1) stage(tb);
-    const uint32_t ip = (uint32_t)(tb - chunk0) * ROW + in_at;
+    if (on_hold_grid(tb)) hold_rows(tb);
+    const uint32_t ip = (uint32_t)(tb - raw0) * ROW + in_at;
     uint4 in[kB];
 #pragma unroll
-    for (int u = 0; u < kB; u++) in[u] = lds_rec[ip + u * ROW];
+    for (int u = 0; u < kB; u++) in[u] = tab_rec(lds_raw[ip + u * ROW]);
 #pragma unroll
     for (int u = 0; u < kB; u++)
       if (u < count) step(EdgeStep(), tb + u, in[u], (uint32_t)(u * kSlot));
@@ -1127,6 +1136,29 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
     for (; t < core_end && ((t - p.f0) & (kB - 1)) != 0; ++t) general(t);
   }
   const int32_t n_core = t + kB <= core_end ? (core_end - t) / kB : 0;
+  // A core block's LDS reads, in two parts so that the loop issues them one block ahead: the raw
+  // bytes of steps t .. t + 7 and (split kernel) of the row the lane's batch sub-step takes,
+  // t + (j & 7) + 1; then their records.
+  constexpr int kRecs = kSplit ? kB + 1 : kB;
+  constexpr int kAheadAt = 1;  // the core step after which the next block's last records are read
+  auto block_raw = [&](int32_t t, uint32_t(&b)[kRecs]) {
+    const uint32_t ip = (uint32_t)(t - raw0) * ROW + in_at;
+#pragma unroll
+    for (int u = 0; u < kB; u++) b[u] = lds_raw[ip + u * ROW];
+    if constexpr (kSplit) b[kB] = lds_raw[ip + (uint32_t)((j & (kB - 1)) + 1) * ROW];
+  };
+  auto block_recs = [&](const uint32_t(&b)[kRecs], uint4(&rec)[kRecs]) {
+#pragma unroll
+    for (int u = 0; u < kRecs; u++) rec[u] = tab_rec(b[u]);
+  };
+  uint4 ahead[kRecs];  // the next core block's records
+  if (n_core > 0) {
+    // the first core block's: issued before publish(), whose barrier waits for them anyway
+    if (on_hold_grid(t)) hold_rows(t);
+    uint32_t b[kRecs];
+    block_raw(t, b);
+    block_recs(b, ahead);
+  }
   if constexpr (kSplit) {
     // The steps so far have stored ring and trace cells that the consumer's steps store again
     // (steps t and t + R share a ring cell): those stores have reached memory before the consumer,
@@ -1139,28 +1171,46 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
     pend_ck = pend_first = 0;
     pend_lanes = cmp_lanes;
     glibc_sincosf_domain_raw(__builtin_bit_cast(float, w[4]), &sc_s, &sc_c, &sc_qs, &sc_qc);
-    // the producer is the longer dependent chain: it issues first when both waves of a SIMD are
-    // ready, the consumer fills the cycles it leaves (measured, DESIGN.md §5: 0.154 -> 0.146 ms)
+    // the producer is one dependent chain: it issues first when both waves of a SIMD are ready,
+    // the consumer fills the cycles it leaves (measured, DESIGN.md §5: 0.154 -> 0.146 ms; stamped
+    // per role, the producer then waits a quarter of each block at the barrier for the consumer)
     if constexpr (kSplit) __builtin_amdgcn_s_setprio(1);
     for (int32_t k = 0; k < n_core; ++k, t += kB) {
-      if (((t - p.f0) & (kStage5 - 1)) == 0) stage(t);
-      const uint32_t ip = (uint32_t)(t - chunk0) * ROW + in_at;
-      uint4 in[kB];
+      // Block k's records were read during block k - 1, ahead of its barrier (whose lgkmcnt(0)
+      // waited for them), so no step waits for LDS here -- except where the raw rows are re-read
+      // at block k: that rewrites lds_raw, and the block reads its records again after it.
+      if (k > 0 && on_hold_grid(t) && hold_rows(t)) {
+        uint32_t b[kRecs];
+        block_raw(t, b);
+        block_recs(b, ahead);
+      }
+      // Block k + 1's raw bytes now; the record of its step u once step u here has used the
+      // register (no second set, no copies) -- but step 7's and the batch's after step kAheadAt
+      // into registers of their own, so that the barrier waits for no read issued just before it.
+      // (Past the last core block these are the edge steps' rows, or the slack row, and unused.)
+      uint32_t b[kRecs];
+      block_raw(t + kB, b);
+      uint4 last = ahead[kB - 1];
+      // Split kernel: block k goes into hand-off buffer k & 1, which the consumer read for block
+      // k - 2 before it arrived at the barrier this wave passed last; the barrier below hands
+      // block k over.
+      const uint32_t slot0 = kSplit ? (uint32_t)(k & 1) * (kB * kHSlot) : 0u;
+      if constexpr (kSplit) lds_hrec[(k & 1) * kWave + wl] = ahead[kB];
 #pragma unroll
-      for (int u = 0; u < kB; u++) in[u] = lds_rec[ip + u * ROW];
+      for (int u = 0; u < kB; u++) {
+        step(std::true_type(), t + u, ahead[u], slot0 + (uint32_t)(u * (kSplit ? kHSlot : kSlot)));
+        if (u < kB - 1) ahead[u] = tab_rec(b[u]);
+        if (u == kAheadAt) {
+          last = tab_rec(b[kB - 1]);
+          if constexpr (kSplit) ahead[kB] = tab_rec(b[kB]);
+        }
+      }
+      ahead[kB - 1] = last;
       if constexpr (kSplit) {
-        // Block k goes into hand-off buffer k & 1, which the consumer read for block k - 2 before
-        // it arrived at the barrier this wave passed last; the barrier below hands block k over.
-        const uint32_t hb = (uint32_t)(k & 1) * (kB * kHSlot);
-        lds_hrec[(k & 1) * kWave + wl] = lds_rec[ip + (uint32_t)((j & (kB - 1)) + 1) * ROW];
-#pragma unroll
-        for (int u = 0; u < kB; u++) step(std::true_type(), t + u, in[u], hb + (uint32_t)(u * kHSlot));
         sb = sb + sb_step;
         sb = sb >= tcap ? sb - tcap : sb;
         block_barrier();
       } else {
-#pragma unroll
-        for (int u = 0; u < kB; u++) step(std::true_type(), t + u, in[u], (uint32_t)(u * kSlot));
         batch(std::true_type(), t, kB);
       }
     }
