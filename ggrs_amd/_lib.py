@@ -26,6 +26,9 @@ GGRS_EMIT_CLOSED, GGRS_EMIT_DISCONNECTED = -18, -19  # ggrs_p2p_read_emit_state'
 GGRS_EMIT_ROW_LOST = -20  # ggrs_p2p_read_spectator_emit_state's own status
 GGRS_TIME_SYNC_KEEP = -2 ** 31  # ggrs_p2p_time_sync's remote_advantage: no report at this call
 GGRS_DESYNC_ROW_LOST = -21  # ggrs_p2p_read_desync_state's status
+# ggrs_p2p_poll_endpoints' net_events bits and ggrs_p2p_read_endpoint_state's state
+GGRS_NET_INTERRUPTED, GGRS_NET_RESUMED, GGRS_NET_DISCONNECTED, GGRS_NET_SHUTDOWN = 1, 2, 4, 8
+GGRS_ENDPOINT_RUNNING, GGRS_ENDPOINT_DISCONNECTED, GGRS_ENDPOINT_SHUTDOWN = 0, 1, 2
 # ggrs_wire_unpack's slot_status codes (accepted: tag + 1, empty: 0)
 GGRS_WIRE_E_BINCODE, GGRS_WIRE_E_SHAPE, GGRS_WIRE_E_CAP, GGRS_WIRE_E_CLOCK, GGRS_WIRE_E_RANGE = -22, -23, -24, -25, -26
 NULL_FRAME = -1
@@ -73,6 +76,7 @@ EXPORTS = (
     "ggrs_p2p_set_time_sync", "ggrs_p2p_time_sync", "ggrs_p2p_read_time_sync_state",
     "ggrs_p2p_set_desync_compare", "ggrs_p2p_add_remote_reports", "ggrs_p2p_add_remote_reports_from",
     "ggrs_p2p_compare_reports", "ggrs_p2p_read_desync_events", "ggrs_p2p_read_desync_state",
+    "ggrs_p2p_set_endpoint_poll", "ggrs_p2p_poll_endpoints", "ggrs_p2p_read_endpoint_state",
     "ggrs_spectator_engine_create", "ggrs_spectator_engine_destroy", "ggrs_spectator_engine_config",
     "ggrs_spectator_add_inputs", "ggrs_spectator_add_arrivals", "ggrs_spectator_advance_frames",
     "ggrs_spectator_calls", "ggrs_spectator_synchronize", "ggrs_spectator_read_sessions",

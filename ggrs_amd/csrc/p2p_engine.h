@@ -3,7 +3,8 @@
 // tables, the prediction threshold and disconnects) and p2p_ingest.hip (the packet feed of the
 // scheduled mode) and p2p_emit.hip (its send side) and p2p_spec_emit.hip (the send side towards the
 // sessions' spectators), p2p_time_sync.hip and p2p_desync.hip (time sync and the checksum comparison,
-// which walk the same calls by the same order rule), with the host side the two send sides share (PacketEmitState: configuration
+// which walk the same calls by the same order rule) and p2p_poll.hip (the endpoint poll, which walks the
+// calls before they run), with the host side the two send sides share (PacketEmitState: configuration
 // and call-order checks, the staging of a launch's arrays, the group plan; emit_begin / emit_end: an
 // emit call before and after the unit's kernel launch; EmitCalls: what emit_begin hands the unit for
 // its kernel's parameters).  Host code and plain structs only; no kernels here.
@@ -243,6 +244,18 @@ struct ggrs_p2p_engine {
   int32_t* dcmp_events = nullptr;   // [4][max_events] call, session, frame, local | remote << 16
   unsigned long long* dcmp_count = nullptr;  // the events raised (exact past max_events)
   hipEvent_t dcmp_sync[2] = {nullptr, nullptr};  // ggrs_p2p_add_remote_reports_from: the two streams' order
+  // endpoint poll (ggrs_p2p_set_endpoint_poll; p2p_poll.hip): UdpProtocol::poll's timers, the disconnect
+  // timeout and the endpoint's state per call, before the call runs
+  int32_t endp_on = 0;              // the mode
+  int32_t endp_next = 0;            // the next call to poll
+  uint8_t* endp_staging = nullptr;  // host-sourced calls: the clocks, kinds and the outputs
+  size_t endp_staging_bytes = 0;
+  uint64_t endp_timeout = 0, endp_notify = 0;  // disconnect_timeout, disconnect_notify_start (ms)
+  uint64_t endp_host_clock = 0;     // the last clock a host array gave (a host array never goes below it)
+  int32_t endp_launches = 0;        // launch i reads endp_clock[i & 1] and writes endp_clock[(i + 1) & 1]
+  uint64_t* endp_times = nullptr;   // [kPollTimes][S] the endpoint's Instants (PollTime)
+  int32_t* endp_st = nullptr;       // [kPollFields][S] its flag word and closing call (PollField)
+  uint64_t* endp_clock = nullptr;   // [2] the engine's last clock
   ggrs::SpanTimer timer;
 };
 
@@ -307,6 +320,21 @@ enum DcField : int {
   kDcFirstRemote,
   kDcFields
 };
+// endpoint poll: the per-session times and words kept between launches
+enum PollTime : int {
+  kPollLastRecv = 0,   // last_recv_time
+  kPollLastInputRecv,  // running_last_input_recv
+  kPollLastReport,     // running_last_quality_report
+  kPollShutdown,       // shutdown_timeout
+  kPollTimes
+};
+enum PollField : int {
+  kPollWord = 0,     // notify_sent | event_sent << 1 | state << 2 (poll_device.h)
+  kPollClosedCall,   // the call at which the endpoint went Running -> Disconnected (-1)
+  kPollFields
+};
+// p2p_poll.hip: free the endpoint poll's buffers
+int p2p_poll_free(ggrs_p2p_engine* e);
 // p2p_desync.hip: free the checksum comparison's buffers
 int p2p_desync_free(ggrs_p2p_engine* e);
 // p2p_time_sync.hip: free time sync's own buffers (emit_ll is p2p_emit_free's)

@@ -1732,6 +1732,10 @@ int p2p_sched_advance(ggrs_p2p_engine* e, int32_t n) {
   if ((int64_t)e->current_frame + n > e->next_arrival_call)
     return set_error(GGRS_E_INVALID, "Missing arrivals: arrival rows are queued up to call %d, calls need up to %d",
                      e->next_arrival_call - 1, e->current_frame + n - 1);
+  // the endpoint poll (p2p_poll.hip) delivers a timeout no later than the reference: a call runs after its poll
+  if (e->endp_on && (int64_t)e->current_frame + n > e->endp_next)
+    return set_error(GGRS_E_STATE, "call %d was not polled (ggrs_p2p_poll_endpoints runs before the call)",
+                     std::max(e->current_frame, e->endp_next));
   SchedParams p;
   p.S = e->cfg.num_sessions;
   p.R = e->R;
@@ -1819,6 +1823,7 @@ int ggrs_p2p_set_arrival_schedule(ggrs_p2p_engine_t* e, int32_t on) {
     e->spec.on = 0;  // (and spectator emit)
     e->tsync.on = 0;  // (and time sync)
     e->dcmp.on = 0;  // (and the checksum comparison)
+    e->endp_on = 0;  // (and the endpoint poll)
     return GGRS_OK;
   }
   if (e->cfg.max_prediction + e->cfg.input_delay + 2 >= kQ)

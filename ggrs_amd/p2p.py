@@ -88,6 +88,10 @@ def _bind(L):
     L.ggrs_p2p_compare_reports.argtypes = [vp, i32, i32, P(i32)]
     L.ggrs_p2p_read_desync_events.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, P(i32)]
     L.ggrs_p2p_read_desync_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    u64 = ctypes.c_uint64
+    L.ggrs_p2p_set_endpoint_poll.argtypes = [vp, u64, u64, u64]
+    L.ggrs_p2p_poll_endpoints.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
+    L.ggrs_p2p_read_endpoint_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     for name in _lib.EXPORTS:
         if name.startswith("ggrs_p2p_"):
             getattr(L, name).restype = ctypes.c_int
@@ -496,6 +500,42 @@ class P2PEngine:
         S = self.num_sessions
         out = [np.zeros(S, np.int32) for _ in range(7)] + [np.zeros((2, 32, S), np.int32) for _ in range(2)]
         _lib.check(self._L.ggrs_p2p_read_desync_state(self._h, *(_vp(a) for a in out)))
+        return tuple(out)
+
+    # ---- endpoint poll (include/ggrs_amd.h, ggrs_p2p_*endpoint*; p2p_poll.hip)
+    def set_endpoint_poll(self, disconnect_timeout_ms=2000, disconnect_notify_start_ms=500, start_ms=0):
+        """Every session's UdpProtocol::poll runs on the device (poll_endpoints): the retry and
+        quality-report timers, NetworkInterrupted / NetworkResumed and the disconnect timeout; after
+        set_arrival_schedule, before the first call.  The defaults are the reference's; every clock of
+        the endpoints starts at start_ms.  From then on advance_frames refuses a call not polled."""
+        _lib.check(self._L.ggrs_p2p_set_endpoint_poll(self._h, disconnect_timeout_ms, disconnect_notify_start_ms,
+                                                      start_ms))
+        self.disconnect_timeout_ms, self.disconnect_notify_start_ms = disconnect_timeout_ms, disconnect_notify_start_ms
+
+    def poll_endpoints(self, first_call, n_calls, now_ms, kinds=None, out=None):
+        """The polls of calls first_call .. first_call + n_calls - 1 (in order, each once, after their
+        arrivals were added or packets received, before they run): now_ms [n] uint64 (never
+        decreasing) and kinds [n][S] uint8 (wire.unpack's, None: nothing arrived).  Returns (resend,
+        send_ack, send_report, net_events) [n][S] uint8 as numpy arrays -- or, with out = such a tuple
+        of torch tensors on the engine's device (now_ms then an int64 device tensor holding the u64's
+        bits, kinds a device tensor), fills and returns them; the launch runs on the engine's stream
+        (synchronize() before another stream reads).  net_events holds GGRS_NET_* bits; a
+        GGRS_NET_DISCONNECTED call has the remote players' bits in its events row on the device."""
+        n, S = int(n_calls), self.num_sessions
+        dev = out is not None
+        outs = list(out) if dev else [np.zeros((n, S), np.uint8) for _ in range(4)]
+        ptrs, keep = _lib.marshal([now_ms, kinds] + outs, ((n,),) + ((n, S),) * 5,
+                                  ("int64" if dev else "uint64",) + ("uint8",) * 5, dev)
+        _lib.check(self._L.ggrs_p2p_poll_endpoints(self._h, first_call, n, *ptrs, int(dev)))
+        return tuple(outs)
+
+    def endpoint_state(self):
+        """(state [S] int32: GGRS_ENDPOINT_*; last_recv_ms, last_input_recv_ms, last_report_ms,
+        shutdown_ms [S] uint64; flags [S] int32: bit 0 disconnect_notify_sent, bit 1
+        disconnect_event_sent; closed_call [S] int32: the call that left Running, -1)."""
+        S = self.num_sessions
+        out = [np.zeros(S, np.int32)] + [np.zeros(S, np.uint64) for _ in range(4)] + [np.zeros(S, np.int32) for _ in range(2)]
+        _lib.check(self._L.ggrs_p2p_read_endpoint_state(self._h, *(_vp(a) for a in out)))
         return tuple(out)
 
     KERNEL_FORMS = {"default": 0, "unstaged": 1, "lockstep": 2, "flat": 3, "chains": 4, "flat_queues": 5,

@@ -817,7 +817,8 @@ int ggrs_p2p_read_spectator_emit_state(ggrs_p2p_engine_t* eng, int32_t* next_spe
  *     what a QualityReport sent at this call carries.
  * Not built: the recommendation is reported, not enacted (every session of an engine takes every call);
  * the QualityReport / QualityReply messages are ggrs_wire_unpack's and ggrs_wire_pack's, their 200 ms
- * timer stays with the host, as do NetworkStats' send_queue_len and kbps_sent; fixed-latency engines and peer reports.
+ * timer is ggrs_p2p_poll_endpoints' send_report; NetworkStats' send_queue_len and kbps_sent stay with the
+ * host; fixed-latency engines and peer reports.
  * The scheduled kernels store what they store for packet emit, one word per session and call.
  * Kernel: p2p_time_sync.hip. */
 #define GGRS_TIME_SYNC_KEEP INT32_MIN /* remote_advantage: no QualityReport arrived at this call */
@@ -908,6 +909,99 @@ int ggrs_p2p_read_desync_events(ggrs_p2p_engine_t* eng, int32_t first, int32_t m
 int ggrs_p2p_read_desync_state(ggrs_p2p_engine_t* eng, int32_t* status, int32_t* n_events, int32_t* first_call,
                                int32_t* first_frame, int32_t* first_local, int32_t* first_remote, int32_t* refused,
                                int32_t* history, int32_t* pending);
+
+/* ---- Endpoint poll: every session's UdpProtocol::poll (protocol.rs:329-376) with the clock bookkeeping
+ * of handle_message (:534-551), per call, on the device: the 200 ms retry and quality-report timers
+ * (RUNNING_RETRY_INTERVAL, QUALITY_REPORT_INTERVAL, :17-19), GgrsEvent::NetworkInterrupted and
+ * NetworkResumed, the disconnect timeout's Event::Disconnected and the endpoint's way from Running over
+ * Disconnected to Shutdown (disconnect, :311-319; UDP_SHUTDOWN_TIMER 5000 ms, :21).  One endpoint per
+ * session holds all of its remote players, as in packet emit.  Arrival-schedule mode is required;
+ * lockstep mode, sparse saving, the packet feed, both emits, time sync, the comparison and peers'
+ * disconnect reports combine with it.  Per session last_recv_time, running_last_input_recv,
+ * running_last_quality_report and shutdown_timeout start at start_ms (every Instant of UdpProtocol::new,
+ * :219-220, :227, :252), the state Running, disconnect_notify_sent and disconnect_event_sent false.
+ * All times are u64 milliseconds, nothing is truncated to 32 bits; `<` is strict, as in the reference.
+ * Call c's poll at clock now = now_ms[c], after call c's arrivals were added or its packets received
+ * and before the call runs:
+ *  0. Shutdown: every output 0, nothing changes (:538-541, :373);
+ *  1. k = kinds[c] != 0 (a message was accepted): last_recv_time = now; with disconnect_notify_sent set
+ *     and the state Running the flag is cleared and GGRS_NET_RESUMED raised (:544-551);
+ *  2. decoded = k has the Input bit and, with the packet feed, the feed's status of call c
+ *     (ggrs_p2p_read_packet_results) is >= 0: running_last_input_recv = now, send_ack[c] = 1 (:608, :634);
+ *  3. ext = the call's events byte holds a remote player's bit (a received disconnect_requested, or the
+ *     host's own);
+ *  4. while Running, in poll()'s order: (a) running_last_input_recv + 200 < now: resend[c] = 1,
+ *     running_last_input_recv = now, whether or not anything is pending (emit decides that); (b)
+ *     running_last_quality_report + 200 < now: send_report[c] = 1, running_last_quality_report = now;
+ *     (c) !disconnect_notify_sent and last_recv_time + disconnect_notify_start < now:
+ *     GGRS_NET_INTERRUPTED, the flag set; (d) ext sets disconnect_event_sent; else with the flag clear
+ *     and last_recv_time + disconnect_timeout < now: GGRS_NET_DISCONNECTED, the flag set, the remote
+ *     players' bits OR-ed into the engine's events row of call c on the device, ext = 1; (e) ext: the
+ *     state becomes Disconnected, shutdown_timeout = now + 5000, closed_call = c;
+ *  5. Disconnected at entry: steps 1-3 apply (acks keep flowing, nothing resumes), the timers do not;
+ *     shutdown_timeout < now: the state becomes Shutdown, GGRS_NET_SHUTDOWN raised.
+ * The scheduled kernels, both emits and time sync read the events row, so a timed-out player is
+ * disconnected by call c itself (disconnect_player_at_frame, p2p_session.rs:618-655: the rollback that
+ * replays the player as InputStatus::Disconnected) and the other units close their endpoint at c; a
+ * stopped session gets no special case.  There is no keep_alive output because send_keep_alive
+ * (:344-347) cannot fire: last_send_time is set by every queue_message (:523), send_quality_report sets
+ * running_last_quality_report and then queues (:502, :512), and the constructor initialises the two in
+ * that order, so last_send_time >= running_last_quality_report at every check; both intervals are
+ * 200 ms, so either the report fired in this poll and last_send_time is later than poll's now, or
+ * last_send_time + 200 >= running_last_quality_report + 200 >= now.  ggrs_wire_pack's keep_alive input
+ * stays a caller's option.
+ * Stated divergences: one clock per poll stands for the reference's several Instant::now() reads; a
+ * remote bit given to an endpoint that is already Disconnected changes nothing (the reference cannot
+ * raise a second Event::Disconnected); after Shutdown send_all_messages drops the queue (:401-407) --
+ * the host drops what the other units still produce, by `state`; a player disconnected through a peer's
+ * report (ggrs_p2p_add_peer_reports) reaches endpoint.disconnect() in the reference
+ * (disconnect_player_at_frame, p2p_session.rs:618-652), but the unit reads the events byte alone, so its
+ * endpoint stays Running, its timers keep firing and it can still raise GGRS_NET_INTERRUPTED or
+ * GGRS_NET_DISCONNECTED later -- the two modes run side by side, untested together; a host that wants
+ * the reference's endpoint puts the remote players' bits into that call's events byte as well.
+ * A limit of the input rows, not of this unit: a link that stays silent keeps the row of the last frame
+ * it delivered in use (the repeat-last prediction's base), and once input_capacity further rows have
+ * been added over it the scheduled launch stops the session with GGRS_E_PRECONDITION, where the
+ * reference plays on.  The timeout ends that wait only if it comes first: keep input_capacity above the
+ * calls that disconnect_timeout_ms spans, plus the calls queued ahead.  A session whose remote players
+ * were all disconnected while its link was silent still holds that row: it stops input_capacity calls
+ * after the silence began, so a server retires a timed-out match before then.  Not built: the spectator endpoints'
+ * and the spectator engine's own poll(); NetworkStats::kbps_sent (it sums size_of_val(&Message), a Rust
+ * layout); MAX_EVENT_QUEUE_SIZE (the unit reports per call, the host forms GgrsEvents).
+ * Kernel: p2p_poll.hip (the step: poll_device.h). */
+#define GGRS_NET_INTERRUPTED 1  /* Event::NetworkInterrupted at this call (its payload: disconnect_timeout - notify_start) */
+#define GGRS_NET_RESUMED 2      /* Event::NetworkResumed */
+#define GGRS_NET_DISCONNECTED 4 /* Event::Disconnected raised by the disconnect timeout at this call */
+#define GGRS_NET_SHUTDOWN 8     /* the endpoint went Disconnected -> Shutdown at this call */
+#define GGRS_ENDPOINT_RUNNING 0
+#define GGRS_ENDPOINT_DISCONNECTED 1
+#define GGRS_ENDPOINT_SHUTDOWN 2
+/* Part of the configuration (after ggrs_p2p_set_arrival_schedule(eng, 1), before the first call; a local
+ * and a remote player): the reference's defaults are 2000 and 500 ms (builder.rs:17-18).
+ * disconnect_notify_start_ms > disconnect_timeout_ms is GGRS_E_INVALID (the reference's Duration
+ * subtraction at :353 panics).  GGRS_E_STATE after the first call and on a fixed-latency engine.  From
+ * then on ggrs_p2p_advance_frames returns GGRS_E_STATE, naming the call, for a call that was not polled:
+ * a timeout is never delivered later than the reference delivers it. */
+int ggrs_p2p_set_endpoint_poll(ggrs_p2p_engine_t* eng, uint64_t disconnect_timeout_ms,
+                               uint64_t disconnect_notify_start_ms, uint64_t start_ms);
+/* The polls of calls first_call .. first_call + n_calls - 1: in order, each exactly once, not yet run
+ * (first_call >= ggrs_p2p_calls), their arrivals added or packets received (GGRS_E_INVALID otherwise,
+ * nothing launched).  now_ms [n] u64 never decreases: a host array that does (or starts below the last
+ * host clock) is GGRS_E_INVALID; on the device a value below the engine's last clock, which is kept in
+ * device memory, is taken as that clock.  kinds [n][S] u8 as ggrs_wire_unpack writes it (NULL: nothing
+ * arrived).  Outputs [n][S] u8 each, any may be NULL: resend (ggrs_p2p_emit_packets' input), send_ack and
+ * send_report (ggrs_wire_pack's), net_events (GGRS_NET_* bits).  on_device as ggrs_p2p_emit_packets.
+ * The result does not depend on how the calls are split over invocations.  GGRS_E_STATE without
+ * ggrs_p2p_set_endpoint_poll. */
+int ggrs_p2p_poll_endpoints(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, const uint64_t* now_ms,
+                            const uint8_t* kinds, uint8_t* resend, uint8_t* send_ack, uint8_t* send_report,
+                            uint8_t* net_events, int32_t on_device);
+/* Per session, [num_sessions] each: the state (GGRS_ENDPOINT_*), the four times, flags (bit 0
+ * disconnect_notify_sent, bit 1 disconnect_event_sent) and the call at which the endpoint left Running
+ * (-1).  Any pointer may be NULL. */
+int ggrs_p2p_read_endpoint_state(ggrs_p2p_engine_t* eng, int32_t* state, uint64_t* last_recv_ms,
+                                 uint64_t* last_input_recv_ms, uint64_t* last_report_ms, uint64_t* shutdown_ms,
+                                 int32_t* flags, int32_t* closed_call);
 
 /* ---------------------------------------------------------------------------------------------
  * Spectators: num_sessions independent SpectatorSessions (src/sessions/p2p_spectator_session.rs),
@@ -1116,9 +1210,10 @@ int ggrs_codec_set_direct(int32_t mode);
  *   ChecksumReport (4) = checksum u128 | frame i32                                (26)
  *   KeepAlive (5)      = nothing                                                  (6)
  * handle_message never checks the magic (0.10.2 has no sync handshake): unpack ignores it, pack writes
- * the endpoint's.  What stays with the host: the sockets, the 200 ms timers (which calls set resend,
- * send_report and keep_alive), NetworkStats' send_queue_len and kbps_sent, NetworkInterrupted /
- * NetworkResumed and the disconnect timeouts. */
+ * the endpoint's.  What stays with the host: the sockets and NetworkStats' send_queue_len and kbps_sent.
+ * The 200 ms timers (which calls set resend, send_ack and send_report), NetworkInterrupted /
+ * NetworkResumed and the disconnect timeouts are ggrs_p2p_poll_endpoints' (above; it also states why
+ * keep_alive is never due). */
 #define GGRS_WIRE_INPUT 0
 #define GGRS_WIRE_INPUT_ACK 1
 #define GGRS_WIRE_QUALITY_REPORT 2

@@ -35,6 +35,7 @@ const UNITS: &[(&str, &[&str])] = &[
     ("p2p_time_sync.hip", NONE),
     ("p2p_desync.hip", NONE),
     ("wire.hip", NONE),
+    ("p2p_poll.hip", NONE),
 ];
 
 fn main() {

@@ -58,6 +58,14 @@ pub const GGRS_EMIT_DISCONNECTED: i32 = -19;
 pub const GGRS_EMIT_ROW_LOST: i32 = -20;
 pub const GGRS_TIME_SYNC_KEEP: i32 = i32::MIN;
 pub const GGRS_DESYNC_ROW_LOST: i32 = -21;
+// endpoint poll: ggrs_p2p_poll_endpoints' net_events bits and ggrs_p2p_read_endpoint_state's state
+pub const GGRS_NET_INTERRUPTED: i32 = 1;
+pub const GGRS_NET_RESUMED: i32 = 2;
+pub const GGRS_NET_DISCONNECTED: i32 = 4;
+pub const GGRS_NET_SHUTDOWN: i32 = 8;
+pub const GGRS_ENDPOINT_RUNNING: i32 = 0;
+pub const GGRS_ENDPOINT_DISCONNECTED: i32 = 1;
+pub const GGRS_ENDPOINT_SHUTDOWN: i32 = 2;
 // wire envelope: message tags and ggrs_wire_unpack's slot_status codes (accepted: tag + 1, empty: 0)
 pub const GGRS_WIRE_INPUT: i32 = 0;
 pub const GGRS_WIRE_INPUT_ACK: i32 = 1;
@@ -472,6 +480,35 @@ extern "C" {
         refused: *mut i32,
         history: *mut i32,
         pending: *mut i32,
+    ) -> i32;
+    // endpoint poll (p2p_poll.hip): UdpProtocol::poll's timers and the disconnect timeout per call, on the device
+    pub fn ggrs_p2p_set_endpoint_poll(
+        eng: *mut ggrs_p2p_engine_t,
+        disconnect_timeout_ms: u64,
+        disconnect_notify_start_ms: u64,
+        start_ms: u64,
+    ) -> i32;
+    pub fn ggrs_p2p_poll_endpoints(
+        eng: *mut ggrs_p2p_engine_t,
+        first_call: i32,
+        n_calls: i32,
+        now_ms: *const u64,
+        kinds: *const u8,
+        resend: *mut u8,
+        send_ack: *mut u8,
+        send_report: *mut u8,
+        net_events: *mut u8,
+        on_device: i32,
+    ) -> i32;
+    pub fn ggrs_p2p_read_endpoint_state(
+        eng: *mut ggrs_p2p_engine_t,
+        state: *mut i32,
+        last_recv_ms: *mut u64,
+        last_input_recv_ms: *mut u64,
+        last_report_ms: *mut u64,
+        shutdown_ms: *mut u64,
+        flags: *mut i32,
+        closed_call: *mut i32,
     ) -> i32;
 
     // ---- spectators (src/sessions/p2p_spectator_session.rs), batched
