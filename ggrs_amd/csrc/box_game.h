@@ -10,6 +10,9 @@
 // (compile with -ffp-contract=off; Rust never contracts), correctly rounded f32 sqrt and division
 // (hipcc's default), f32 denormals kept (hipcc's default), glibc's own sinf/cosf algorithm
 // (glibc_sincosf.h), exact fmodf for rem_euclid.
+// Every form of the step below, the hooks and the Fletcher-16 are compared with the CPU oracle on
+// the device, one step from arbitrary states: tests/test_gpu_step_forms.py (DESIGN.md section 3 lists
+// which of its tests pins which form).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -170,7 +173,9 @@ __device__ inline float sqrt_rn_above_49(float s) {
 // operands the exact quotient lies at least 2^-49 (relative) away from every f32 rounding
 // boundary (midpoint), so a binary64 value within 2^-50.5 of it rounds to the same f32 as the
 // exact quotient: RN32(q64) == RN32(a / m).  Checked against hipcc's correctly rounded division
-// on the GPU (tests/test_gpu_sincosf.py).  m is finite, > 7 here.
+// on the GPU (tests/test_gpu_sincosf.py, test_clamp_division_through_f64_reciprocal), and inside the
+// step against the oracle's division around mag2 == 49 (tests/test_gpu_step_forms.py).  m is finite,
+// > 7 here.
 __device__ inline double rcp_f64_refined(double d) {
   double r = __builtin_amdgcn_rcp(d);
   double e = __builtin_fma(-d, r, 1.0);
@@ -188,7 +193,8 @@ __device__ inline double rcp_f64_refined(double d) {
 //   * max(min(.)) clamps become v_med3_f32: equal for every non-NaN input without -0, and a
 //     position sum is never -0 (x >= +0, and x + v == 0 only as +0) nor NaN.
 //   * the turn's rem_euclid on [-RS, 2pi + RS] is one add or subtract of 2pi chosen by two
-//     compares (every rot in the domain, both directions: tests/native/remeuclid_kat_host.c).
+//     compares (every rot in the domain, both directions: tests/native/remeuclid_kat_host.c; on the
+//     device, the wrap and quadrant edges: tests/test_gpu_step_forms.py, class "rotation edges").
 typedef float ggrs_f2 __attribute__((ext_vector_type(2)));
 struct NoHook {
   __device__ void operator()(float) const {}
@@ -285,7 +291,8 @@ __device__ inline void advance_player_rec(float& x, float& y, float& vx, float& 
   ggrs_f2 vel = ggrs_f2{vx, vy} * kFriction;
   const ggrs_f2 d = ggrs_f2{c, s} * kMovementSpeed;
   // (elements copied out first: __builtin_bit_cast of an ext_vector element lvalue read element 0
-  // for both -- seen with this image's hipcc, caught by the device KAT)
+  // for both -- seen with this image's hipcc, caught by the device KAT; the oracle KAT of this form
+  // is test_gpu_step_forms.py::test_step_form[rec-*])
   const float dx = d.x, dy = d.y;
   const uint32_t ix = ((__builtin_bit_cast(uint32_t, dx) ^ in.sgn) & in.keep) | (in.sgn & ~in.keep);
   const uint32_t iy = ((__builtin_bit_cast(uint32_t, dy) ^ in.sgn) & in.keep) | (in.sgn & ~in.keep);
@@ -315,6 +322,8 @@ __device__ inline void advance_player_rec(float& x, float& y, float& vx, float& 
 // velocity increment keep ? (d ^ q ^ sgn) : sgn of advance_player_rec (d = MOVEMENT_SPEED times the
 // signed sin/cos) with d = MOVEMENT_SPEED x the raw value, whose sign q is applied as a bit flip
 // after the multiplication (RN(k * -v) == -RN(k * v) exactly): (d & keep) ^ (sgn ^ (q & keep)).
+// KATs against the oracle: test_gpu_step_forms.py::test_step_form[rec_q-*], and test_chain with the
+// next step's raw sin/cos computed in the hook.
 template <typename Hook = NoHook>
 __device__ inline void advance_player_rec_q(float& x, float& y, float& vx, float& vy, float& rot, const InputRec& in,
                                             float sr, float cr, uint32_t qs, uint32_t qc, Hook&& hook = Hook()) {
@@ -359,6 +368,8 @@ __device__ inline void advance_player_lean(float& x, float& y, float& vx, float&
 // player step would cut the N step chains into N basic blocks, which the scheduler cannot
 // interleave; with one, a wave alone on its SIMD issues the N chains side by side.
 // v[i] = {x, y, vx, vy, rot} bits of player step i, in[i] its input.
+// KAT against the oracle (the clamp on each player alone and on all): test_gpu_step_forms.py::
+// test_players_form, for this form and advance_players_rec.
 template <int N>
 __device__ inline void advance_players_lean(uint32_t (&v)[N][5], const uint32_t (&in)[N],
                                             const SincosConsts& K = sincos_consts_vgpr()) {
@@ -458,7 +469,9 @@ __device__ inline void advance_players_rec(uint32_t (&v)[N][5], const InputRec (
 
 // Dispatch (every kernel): the lean branch-free form when every active lane's rot is in the
 // domain (always, for states this engine produced), else the general form for the whole wave.
-// advance_player_domain stays as the KAT reference of the lean form.
+// advance_player_domain stays as the device-side KAT reference of the lean form
+// (tests/test_gpu_sincosf.py); both branches and waves that mix them are compared with the oracle in
+// test_gpu_step_forms.py::test_step_form[dispatch-*] and test_state_form[state-*].
 __device__ inline void advance_player(float& x, float& y, float& vx, float& vy, float& rot, uint32_t input) {
   const bool in_domain = __builtin_bit_cast(uint32_t, rot) <= kTwoPiBits;
   if (__builtin_expect(__all(in_domain), 1)) advance_player_lean(x, y, vx, vy, rot, input);
@@ -629,7 +642,9 @@ __device__ inline uint16_t fletcher16_state(const BoxState<P>& s) {
   return (uint16_t)fletcher_from_doubled(a1 + b1, a2 + b2);
 }
 
-// Host mirror of the same closed form (used by the C ABI's host-side helpers/tests).
+// Host mirror of the same closed form (used by the C ABI's host-side helpers/tests).  Both, and each
+// fletcher_from_doubled variant, against fletcher16 of the bincode bytes on arbitrary words:
+// test_gpu_step_forms.py::test_fletcher.
 template <int P>
 inline uint16_t fletcher16_state_host(const uint32_t* w) {
   constexpr int n = Fletcher<P>::n;

@@ -18,7 +18,8 @@
 //
 // Verified exhaustively against this image's /lib/x86_64-linux-gnu/libm.so.6 on ALL 2^32 f32
 // inputs (sin, cos and the fused form; tests/test_sincosf_kat.py, CPU) and on the device over
-// every f32 in [0, 2*pi] (tests/test_gpu_sincosf.py).
+// every f32 in [0, 2*pi] (tests/test_gpu_sincosf.py: glibc_sinf / glibc_cosf / glibc_sincosf_small;
+// tests/test_gpu_step_forms.py::test_domain_digest: the four _domain forms the kernels call).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -194,7 +195,8 @@ __host__ __device__ inline void glibc_sincosf_small(float y, float* sinp, float*
 // with the reduction path: for y < 0.75 (the |y| < pi/4 test of abstop12) reduce_fast yields
 // n = 0 and x - 0*hpi = x exactly, and the |y| < 2^-12 shortcut (sin = y, cos = 1) is what the
 // polynomials round to there.  Verified against libm on every f32 of the domain
-// (tests/native/sincosf_kat_host.cpp, bad_domain).
+// (tests/native/sincosf_kat_host.cpp, bad_domain, on the host; test_gpu_step_forms.py::
+// test_domain_digest on the device, for this form, _k, _raw and _raw_k).
 //
 // The reduction without integer conversions: reduce_fast's n = ((int32_t)(x * hpi_inv) +
 // 2^23) >> 24 is floor(x * hpi_inv * 2^-24 + 1/2) for x >= 0 (floor((floor(r) + k) / m) =

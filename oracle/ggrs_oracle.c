@@ -690,6 +690,35 @@ static void state_from_bytes(State* s, const uint8_t* b) {
 void oracle_state_advance_bytes(const uint8_t* in, const uint8_t* inputs, const uint8_t* status, uint8_t* out) {
   State s; state_from_bytes(&s, in); state_advance(&s, inputs, status); oracle_state_serialize(&s, out); state_free(&s);
 }
+/* Single-step batch entries (for the device step-form KATs, tests/test_gpu_step_forms.py).
+ * ship_step on n independent player states given as raw bits: in / out [n][5] = x, y, vx, vy, rot. */
+void oracle_ship_step_batch(int64_t n, const uint32_t* in, const uint8_t* input, uint32_t* out) {
+  for (int64_t i = 0; i < n; i++) {
+    float v[5];
+    memcpy(v, in + 5 * i, sizeof v);
+    ship_step(&v[0], &v[1], &v[2], &v[3], &v[4], input[i]);
+    memcpy(out + 5 * i, v, sizeof v);
+  }
+}
+/* State::advance on n whole P-player states: in / out [n][36+20P] bincode bytes, inputs and status
+ * [n][P] (status NULL: every player Confirmed).  Returns -1 for a state whose num_players is not P. */
+int oracle_state_advance_batch(int32_t P, int64_t n, const uint8_t* in, const uint8_t* inputs, const uint8_t* status,
+                               uint8_t* out) {
+  if (P < 1 || P > MAX_PLAYERS) return -1;
+  const size_t sb = 36 + 20 * (size_t)P;
+  const uint8_t confirmed[MAX_PLAYERS] = {0};
+  for (int64_t i = 0; i < n; i++) {
+    uint64_t p; memcpy(&p, in + (size_t)i * sb + 4, 8);
+    if (p != (uint64_t)P) return -1;
+    oracle_state_advance_bytes(in + (size_t)i * sb, inputs + (size_t)i * P, status ? status + (size_t)i * P : confirmed,
+                               out + (size_t)i * sb);
+  }
+  return 0;
+}
+/* oracle_fletcher16 of n byte strings of `len` bytes each. */
+void oracle_fletcher16_batch(int64_t n, size_t len, const uint8_t* data, uint16_t* out) {
+  for (int64_t i = 0; i < n; i++) out[i] = oracle_fletcher16(data + (size_t)i * len, len);
+}
 float oracle_sinf(float x) { return sinf(x); }
 float oracle_cosf(float x) { return cosf(x); }
 float oracle_fmodf(float a, float b) { return fmodf(a, b); }

@@ -177,6 +177,62 @@ def state_advance(state, inputs, status=None):
     return out
 
 
+def _bind_step_batch(L):
+    if getattr(L, "_step_batch_bound", False):
+        return
+    P = ctypes.POINTER
+    u8p, u16p, u32p = P(ctypes.c_uint8), P(ctypes.c_uint16), P(ctypes.c_uint32)
+    L.oracle_ship_step_batch.argtypes = [ctypes.c_int64, u32p, u8p, u32p]
+    L.oracle_ship_step_batch.restype = None
+    L.oracle_state_advance_batch.argtypes = [ctypes.c_int32, ctypes.c_int64, u8p, u8p, u8p, u8p]
+    L.oracle_state_advance_batch.restype = ctypes.c_int
+    L.oracle_fletcher16_batch.argtypes = [ctypes.c_int64, ctypes.c_size_t, u8p, u16p]
+    L.oracle_fletcher16_batch.restype = None
+    L._step_batch_bound = True
+
+
+def ship_step_batch(players, inputs):
+    """One ex_game player step (ship_step) on n independent player states: players [n][5] u32 raw
+    bits of x, y, vx, vy, rot, inputs [n] u8 (Input.inp); returns the stepped [n][5] u32."""
+    pl = np.ascontiguousarray(players, np.uint32).reshape(-1, 5)
+    inp = np.ascontiguousarray(inputs, np.uint8).reshape(-1)
+    assert inp.size == pl.shape[0]
+    out = np.zeros_like(pl)
+    L = lib()
+    _bind_step_batch(L)
+    L.oracle_ship_step_batch(pl.shape[0], _ptr(pl, ctypes.c_uint32), _ptr(inp, ctypes.c_uint8),
+                             _ptr(out, ctypes.c_uint32))
+    return out
+
+
+def state_advance_batch(states, inputs, status=None):
+    """State::advance on n whole states: states [n][36+20P] bincode bytes, inputs [n][P], status
+    [n][P] InputStatus (None: all Confirmed); returns the advanced [n][36+20P] bytes."""
+    st = np.ascontiguousarray(states, np.uint8)
+    n, sb = st.shape
+    p = (sb - 36) // 20
+    inp = np.ascontiguousarray(inputs, np.uint8).reshape(n, p)
+    sta = None if status is None else np.ascontiguousarray(status, np.uint8).reshape(n, p)
+    out = np.zeros_like(st)
+    L = lib()
+    _bind_step_batch(L)
+    rc = L.oracle_state_advance_batch(p, n, _ptr(st, ctypes.c_uint8), _ptr(inp, ctypes.c_uint8),
+                                      _ptr(sta, ctypes.c_uint8), _ptr(out, ctypes.c_uint8))
+    if rc != 0:
+        raise ValueError("bad state batch: num_players differs from the row size")
+    return out
+
+
+def fletcher16_batch(rows):
+    """fletcher16 of every row of rows [n][len] u8; returns [n] u16."""
+    a = np.ascontiguousarray(rows, np.uint8)
+    out = np.zeros(a.shape[0], np.uint16)
+    L = lib()
+    _bind_step_batch(L)
+    L.oracle_fletcher16_batch(a.shape[0], a.shape[1], _ptr(a, ctypes.c_uint8), _ptr(out, ctypes.c_uint16))
+    return out
+
+
 def synctest_run(inputs, num_players=2, max_prediction=8, check_distance=2, input_delay=0,
                  random_checksums=False, rng_seed=1, req_cap=None, corrupt_frame=-1):
     """Run the restated SyncTest loop; returns a dict of numpy arrays and the result struct."""

@@ -6,10 +6,11 @@ and the fused form.  The v4 step (advance_player_lean): its clamp square root on
 import ctypes
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
+
+from tests.step_form_cases import compile_kat
 
 pytestmark = pytest.mark.gpu
 
@@ -20,13 +21,9 @@ GOLDEN = json.load(open(os.path.join(HERE, "golden", "golden.json")))
 
 @pytest.fixture(scope="module")
 def katlib(tmp_path_factory):
-    so = os.path.join(HERE, "native", "libsincosf_kat_device.so")
-    src = os.path.join(HERE, "native", "sincosf_kat_device.hip")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-ffp-contract=off",
-                        "-fPIC", "-shared", "-std=c++17", "-I", os.path.join(ROOT, "ggrs_amd", "csrc"),
-                        src, "-o", so], check=True)
-    L = ctypes.CDLL(so)
+    # compiled afresh every session: a library kept from an earlier build would not see an edit to the
+    # headers under test (glibc_sincosf.h, box_game.h)
+    L = ctypes.CDLL(compile_kat("sincosf_kat_device", tmp_path_factory.mktemp("sincosf_kat")))
     L.kat_digest.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
     L.kat_values.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.kat_sqrt49.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
