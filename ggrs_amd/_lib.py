@@ -77,12 +77,14 @@ EXPORTS = (
     "ggrs_p2p_set_desync_compare", "ggrs_p2p_add_remote_reports", "ggrs_p2p_add_remote_reports_from",
     "ggrs_p2p_compare_reports", "ggrs_p2p_read_desync_events", "ggrs_p2p_read_desync_state",
     "ggrs_p2p_set_endpoint_poll", "ggrs_p2p_poll_endpoints", "ggrs_p2p_read_endpoint_state",
+    "ggrs_p2p_set_spectator_poll", "ggrs_p2p_poll_spectator_endpoints", "ggrs_p2p_read_spectator_endpoint_state",
     "ggrs_spectator_engine_create", "ggrs_spectator_engine_destroy", "ggrs_spectator_engine_config",
     "ggrs_spectator_add_inputs", "ggrs_spectator_add_arrivals", "ggrs_spectator_advance_frames",
     "ggrs_spectator_calls", "ggrs_spectator_synchronize", "ggrs_spectator_read_sessions",
     "ggrs_spectator_read_state", "ggrs_spectator_read_states", "ggrs_spectator_read_trace",
     "ggrs_spectator_timing_reset", "ggrs_spectator_timing_stop", "ggrs_spectator_timing_read",
     "ggrs_spectator_set_packet_feed", "ggrs_spectator_receive_packets", "ggrs_spectator_read_packet_results",
+    "ggrs_spectator_set_endpoint_poll", "ggrs_spectator_poll_endpoints", "ggrs_spectator_read_endpoint_state",
     "ggrs_codec_encode", "ggrs_codec_decode", "ggrs_codec_encode_chunked", "ggrs_codec_decode_chunked", "ggrs_codec_max_packet_bytes", "ggrs_codec_set_direct",
     "ggrs_wire_max_datagram_bytes", "ggrs_wire_unpack", "ggrs_wire_pack",
 )

@@ -18,6 +18,7 @@
 #include "codec_device.h"
 #include "common.h"
 #include "p2p_plan.h"
+#include "poll_host.h"
 
 namespace ggrs {
 // the two emits: PENDING_OUTPUT_SIZE (protocol.rs:22); the kernels' block (one wave of sessions), the
@@ -256,6 +257,10 @@ struct ggrs_p2p_engine {
   uint64_t* endp_times = nullptr;   // [kPollTimes][S] the endpoint's Instants (PollTime)
   int32_t* endp_st = nullptr;       // [kPollFields][S] its flag word and closing call (PollField)
   uint64_t* endp_clock = nullptr;   // [2] the engine's last clock
+  // spectator endpoint poll (ggrs_p2p_set_spectator_poll; p2p_spec_poll.hip): the same for the spec_k
+  // endpoints a session has towards its spectators, [..][spec_k][S] rows; spectator emit reads its
+  // closed_call row
+  ggrs::PollHost spoll;
   ggrs::SpanTimer timer;
 };
 
@@ -320,21 +325,10 @@ enum DcField : int {
   kDcFirstRemote,
   kDcFields
 };
-// endpoint poll: the per-session times and words kept between launches
-enum PollTime : int {
-  kPollLastRecv = 0,   // last_recv_time
-  kPollLastInputRecv,  // running_last_input_recv
-  kPollLastReport,     // running_last_quality_report
-  kPollShutdown,       // shutdown_timeout
-  kPollTimes
-};
-enum PollField : int {
-  kPollWord = 0,     // notify_sent | event_sent << 1 | state << 2 (poll_device.h)
-  kPollClosedCall,   // the call at which the endpoint went Running -> Disconnected (-1)
-  kPollFields
-};
 // p2p_poll.hip: free the endpoint poll's buffers
 int p2p_poll_free(ggrs_p2p_engine* e);
+// p2p_spec_poll.hip: free the spectator endpoint poll's buffers (and turn it off)
+int p2p_spec_poll_free(ggrs_p2p_engine* e);
 // p2p_desync.hip: free the checksum comparison's buffers
 int p2p_desync_free(ggrs_p2p_engine* e);
 // p2p_time_sync.hip: free time sync's own buffers (emit_ll is p2p_emit_free's)

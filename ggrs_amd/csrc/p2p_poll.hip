@@ -17,14 +17,9 @@
 // raise a second Event::Disconnected); after Shutdown send_all_messages drops the queue (:401-407),
 // here the host drops what the other units still produce, by the state.
 //
-// One thread per session, one wave per block; the launch's calls are walked in order because the
-// times carry from call to call.  The four times and the flag word live in registers for the launch,
-// loaded from and stored to [fields][S] rows.  The clock of a call is wave-uniform: now_ms and the
-// engine's last clock come through the scalar path.  A group of calls' kinds, status and events bytes
-// is loaded before its first use; the outputs are coalesced [S] byte stores; the events row is
-// written by the lanes that added a bit, each its own byte.  No LDS, no scratch.  The last clock is
-// kept in device memory in two slots, read from one and written to the other by alternate launches:
-// a block that starts late must not read what the first block already wrote.
+// One thread per session; the launch loop is poll_device.h's poll_walk, shared with the two spectator
+// units.  This unit's own part: the call's events byte is read from and, by the lanes whose timeout
+// fired, written to the engine's events row, each lane its own byte.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,96 +34,36 @@ using namespace ggrs;
 
 namespace {
 
-constexpr int kPollBlock = kEmitBlock;
-constexpr int kPollGroup = kEmitGroup;
+static_assert(kPollBlock == kEmitBlock && kPollGroup == kEmitGroup, "the poll walks the emits' block and group");
 
 struct PollParams {
-  int64_t S;
-  int32_t cap, c0, n;
-  int32_t pkt;
+  PollWalk w;
+  int32_t cap, pkt;
   uint32_t rmask;              // the remote players' event bits
-  uint64_t timeout, notify;
-  const uint64_t* now;         // [n]
-  const uint64_t* clock_in;    // the engine's last clock before the launch
-  uint64_t* clock_out;         // ... and after it
   const uint8_t* kinds;        // [n][S] or null
   const int32_t* status;       // [cap][S] the feed's status row (the packet feed on)
   uint8_t* events;             // [cap][S]
-  uint64_t* times;             // [kPollTimes][S]
-  int32_t* st;                 // [kPollFields][S]
-  uint8_t* o_resend;           // [n][S] each, or null
-  uint8_t* o_ack;
-  uint8_t* o_report;
-  uint8_t* o_net;
+};
+
+struct RemoteIo {
+  const PollParams& p;
+  __device__ inline void begin(int64_t) {}
+  __device__ inline void load(int32_t k, int32_t c, int64_t s, uint32_t& kd, uint32_t& ev, int32_t& st) const {
+    const int64_t o = (int64_t)(c % p.cap) * p.w.E + s;
+    kd = p.kinds ? p.kinds[(int64_t)k * p.w.E + s] : 0u;
+    ev = p.events[o];
+    st = p.pkt ? p.status[o] : 0;
+  }
+  __device__ inline bool decoded(uint32_t kd, int32_t st) const { return (kd & (1u << GGRS_WIRE_INPUT)) != 0 && st >= 0; }
+  __device__ inline uint32_t ext(uint32_t ev) const { return (ev & p.rmask) != 0 ? kPollExt : 0u; }
+  // the timeout's Event::Disconnected: the call itself disconnects the remote players
+  __device__ inline void raised(int32_t c, int64_t s, uint32_t ev) const {
+    p.events[(int64_t)(c % p.cap) * p.w.E + s] = (uint8_t)(ev | p.rmask);
+  }
 };
 
 __global__ __launch_bounds__(kPollBlock) void p2p_poll_kernel(PollParams p) {
-  const int t = threadIdx.x;
-  const int64_t S = p.S;
-  const int64_t s0 = (int64_t)blockIdx.x * kPollBlock;
-  const int nb = (int)min((int64_t)kPollBlock, S - s0);
-  const bool live = t < nb;
-  const int64_t s = live ? s0 + t : s0;  // idle lanes shadow the block's first session, never store
-  const int32_t cap = p.cap;
-  PollEndpoint ep;
-  ep.last_recv = p.times[(int64_t)kPollLastRecv * S + s];
-  ep.last_input_recv = p.times[(int64_t)kPollLastInputRecv * S + s];
-  ep.last_report = p.times[(int64_t)kPollLastReport * S + s];
-  ep.shutdown = p.times[(int64_t)kPollShutdown * S + s];
-  ep.word = (uint32_t)p.st[(int64_t)kPollWord * S + s];
-  ep.closed_call = p.st[(int64_t)kPollClosedCall * S + s];
-  uint64_t clock = *p.clock_in;
-
-  for (int32_t k0 = 0; k0 < p.n; k0 += kPollGroup) {
-    const int gn = min(kPollGroup, p.n - k0);
-    // the group's per-call bytes, all loads in flight together (a short group repeats its last call)
-    uint32_t kd8[kPollGroup], ev8[kPollGroup];
-    int32_t st8[kPollGroup];
-#pragma unroll
-    for (int g = 0; g < kPollGroup; g++) {
-      const int32_t k = k0 + min(g, gn - 1);
-      const int64_t o = (int64_t)((p.c0 + k) % cap) * S + s;
-      kd8[g] = p.kinds ? p.kinds[(int64_t)k * S + s] : 0u;
-      ev8[g] = p.events[o];
-      st8[g] = p.pkt ? p.status[o] : 0;
-    }
-    for (int g = 0; g < gn; g++) {
-      const int32_t c = p.c0 + k0 + g;
-      // an Instant never goes back: a clock below the engine's last is taken as that
-      const uint64_t now = max(p.now[k0 + g], clock);
-      clock = now;
-      // this call's bytes: the front of the batch, which shifts down a call per iteration (indexing it
-      // by g would put it in scratch memory)
-      const uint32_t kd = kd8[0], ev = ev8[0];
-      const int32_t status = st8[0];
-#pragma unroll
-      for (int j = 0; j < kPollGroup - 1; j++) {
-        kd8[j] = kd8[j + 1];
-        ev8[j] = ev8[j + 1];
-        st8[j] = st8[j + 1];
-      }
-      const bool decoded = (kd & (1u << GGRS_WIRE_INPUT)) != 0 && status >= 0;
-      const uint32_t r = poll_endpoint_step(ep, now, p.timeout, p.notify, c, kd != 0, decoded, (ev & p.rmask) != 0);
-      if (live) {
-        const int64_t o = (int64_t)(k0 + g) * S + s;
-        if (p.o_resend) p.o_resend[o] = (uint8_t)((r & kPollResend) != 0);
-        if (p.o_ack) p.o_ack[o] = (uint8_t)((r & kPollSendAck) != 0);
-        if (p.o_report) p.o_report[o] = (uint8_t)((r & kPollSendReport) != 0);
-        if (p.o_net) p.o_net[o] = (uint8_t)(r & 15u);
-        // the timeout's Event::Disconnected: the call itself disconnects the remote players
-        if (r & GGRS_NET_DISCONNECTED) p.events[(int64_t)(c % cap) * S + s] = (uint8_t)(ev | p.rmask);
-      }
-    }
-  }
-  if (live) {
-    p.times[(int64_t)kPollLastRecv * S + s] = ep.last_recv;
-    p.times[(int64_t)kPollLastInputRecv * S + s] = ep.last_input_recv;
-    p.times[(int64_t)kPollLastReport * S + s] = ep.last_report;
-    p.times[(int64_t)kPollShutdown * S + s] = ep.shutdown;
-    p.st[(int64_t)kPollWord * S + s] = (int32_t)ep.word;
-    p.st[(int64_t)kPollClosedCall * S + s] = ep.closed_call;
-  }
-  if (blockIdx.x == 0 && t == 0) *p.clock_out = clock;
+  poll_walk<PollOwner::kSessionRemote>(p.w, RemoteIo{p});
 }
 
 __global__ void poll_fill_kernel(uint64_t* a, int64_t n, uint64_t v) {
@@ -243,9 +178,9 @@ int ggrs_p2p_poll_endpoints(ggrs_p2p_engine_t* e, int32_t first_call, int32_t n,
   if (int rc = e->timer.before(e->stream)) return rc;
   const uint32_t rmask = ~(uint32_t)e->cfg.local_mask & ((1u << e->cfg.num_players) - 1u);
   const int in = e->endp_launches & 1;
-  const PollParams p{(int64_t)S, e->cap, first_call, n, e->pkt, rmask, e->endp_timeout, e->endp_notify, d_now,
-                     e->endp_clock + in, e->endp_clock + (in ^ 1), d_kinds, e->feed.status, e->events, e->endp_times,
-                     e->endp_st, d_out[0], d_out[1], d_out[2], d_out[3]};
+  const PollParams p{{(int64_t)S, first_call, n, e->endp_timeout, e->endp_notify, d_now, e->endp_clock + in,
+                      e->endp_clock + (in ^ 1), e->endp_times, e->endp_st, d_out[0], d_out[1], d_out[2], d_out[3]},
+                     e->cap, e->pkt, rmask, d_kinds, e->feed.status, e->events};
   p2p_poll_kernel<<<grid_of((int64_t)S, kPollBlock), kPollBlock, 0, e->stream>>>(p);
   HIP_TRY(hipGetLastError());
   e->timer.count();

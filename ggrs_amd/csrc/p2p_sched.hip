@@ -1824,6 +1824,7 @@ int ggrs_p2p_set_arrival_schedule(ggrs_p2p_engine_t* e, int32_t on) {
     e->tsync.on = 0;  // (and time sync)
     e->dcmp.on = 0;  // (and the checksum comparison)
     e->endp_on = 0;  // (and the endpoint poll)
+    e->spoll.on = 0;  // (and the spectator endpoints')
     return GGRS_OK;
   }
   if (e->cfg.max_prediction + e->cfg.input_delay + 2 >= kQ)

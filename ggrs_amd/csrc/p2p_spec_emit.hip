@@ -48,6 +48,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "codec_device.h"
 #include "common.h"
@@ -79,13 +80,18 @@ struct SpecParams {
   uint32_t* ring;              // [Q][S]
   int32_t* st;                 // [kSpecFields][S]
   int32_t* ep;                 // [kSpecEpFields][K][S]
+  const int32_t* poll_closed;  // [K][S] the spectator endpoint poll's closed_call (kPoll)
   int32_t* o_start;            // [n][K][S]
   int32_t* o_len;              // [n][K][S]
   int32_t* o_notes;            // [n][S]
   uint8_t* o_packets;          // [n][K][S][stride]
 };
 
-template <int P>
+// kPoll: the engine polls its spectator endpoints (p2p_spec_poll.hip).  An endpoint the poll closed at a
+// call <= c pushes and emits nothing from call c on, a retry included: its status becomes
+// GGRS_EMIT_CLOSED and its closing call the poll's (send_input's early return and the is_running()
+// check, protocol.rs:426, p2p_session.rs:736).  The session and its other endpoints are untouched.
+template <int P, bool kPoll>
 __global__ __launch_bounds__(kEmitBlock) void p2p_spec_emit_kernel(SpecParams p) {
   // [G][kEmitBlock][pitch] the packet rows of a group of (call, endpoint) pairs, then their lengths
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -125,6 +131,7 @@ __global__ __launch_bounds__(kEmitBlock) void p2p_spec_emit_kernel(SpecParams p)
   int32_t e_la[kSpecMaxK], e_pend[kSpecMaxK], e_status[kSpecMaxK], e_closed[kSpecMaxK];
   uint32_t e_lab[kSpecMaxK];
   int32_t sent_slot[kSpecMaxK], sent_len[kSpecMaxK];
+  int32_t e_pc[kSpecMaxK];  // (kPoll) the poll's closing call
   auto epf = [&](int f, int j) -> int32_t& { return p.ep[((int64_t)f * K + j) * S + s]; };
 #pragma unroll
   for (int j = 0; j < kSpecMaxK; j++) {
@@ -134,6 +141,8 @@ __global__ __launch_bounds__(kEmitBlock) void p2p_spec_emit_kernel(SpecParams p)
     e_pend[j] = epf(kSpecEpPending, jj);
     e_status[j] = epf(kSpecEpStatus, jj);
     e_closed[j] = epf(kSpecEpClosedCall, jj);
+    e_pc[j] = -1;
+    if constexpr (kPoll) e_pc[j] = p.poll_closed[(int64_t)jj * S + s];
     sent_slot[j] = -1;
     sent_len[j] = 0;
   }
@@ -258,6 +267,15 @@ __global__ __launch_bounds__(kEmitBlock) void p2p_spec_emit_kernel(SpecParams p)
             la = e_la[j];
             lab = e_lab[j];
           }
+        if constexpr (kPoll) {
+#pragma unroll
+          for (int j = 0; j < kSpecMaxK; j++)
+            if (j == k && status == 0 && e_pc[j] >= 0 && e_pc[j] <= c) {
+              status = GGRS_EMIT_CLOSED;
+              e_status[j] = status;
+              e_closed[j] = e_pc[j];
+            }
+        }
         // (the pair's ack and retry flag were loaded a pair ahead; the next pair's loads go out now)
         const int32_t ack = n_ack;
         const uint32_t rs = n_rs;
@@ -426,6 +444,7 @@ int ggrs_p2p_set_spectator_emit(ggrs_p2p_engine_t* e, int32_t num_spectators, in
   constexpr uint32_t kEpZero = 1u << kSpecEpLaBytes | 1u << kSpecEpPending | 1u << kSpecEpStatus;
   if (int rc = emit_fill(e->spec_ep, K * S, kSpecEpFields, kEpZero, e->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));
+  p2p_spec_poll_free(e);  // (the spectator endpoint poll is configured after this, over these K endpoints)
   e->spec.configure(max_pending_inputs, out_stride);
   e->spec_k = (int32_t)K;
   e->spec_q = Q;
@@ -437,6 +456,9 @@ int ggrs_p2p_emit_spectator_packets(ggrs_p2p_engine_t* e, int32_t first_call, in
                                     uint8_t* packets, int32_t on_device) {
   if (!e) return set_error(GGRS_E_INVALID, "null engine");
   if (!e->sched || !e->spec.on) return set_error(GGRS_E_STATE, "emitting spectator packets needs ggrs_p2p_set_spectator_emit");
+  if (e->spoll.on && n > 0 && (int64_t)first_call + n > e->spoll.next)
+    return set_error(GGRS_E_STATE, "call %d's spectator endpoints were not polled (ggrs_p2p_poll_spectator_endpoints)",
+                     std::max(first_call, e->spoll.next));
   const EmitIo io{ack_in, resend, start_frame, packet_len, notes, packets};
   EmitCalls c;
   size_t lds = 0;
@@ -446,13 +468,21 @@ int ggrs_p2p_emit_spectator_packets(ggrs_p2p_engine_t* e, int32_t first_call, in
   const uint32_t lmask = (uint32_t)e->cfg.local_mask & ((1u << e->cfg.num_players) - 1u);
   const SpecParams p{c.S, c.cap, c.c0, c.n, c.G, e->spec_k, c.maxpend, c.stride, c.Pp, c.pkt, spec_dedup_from_env(),
                      (uint32_t)e->spec_q - 1u, lmask, c.inputs, e->row_tag, c.ll, c.arrive, c.pkt_ack, c.events, c.io.ack_in,
-                     c.io.resend, e->spec_ring, e->spec_st, e->spec_ep, c.io.start, c.io.len, c.io.word, c.io.packets};
+                     c.io.resend, e->spec_ring, e->spec_st, e->spec_ep,
+                     e->spoll.on ? e->spoll.st + (size_t)kPollClosedCall * e->spoll.E : nullptr, c.io.start, c.io.len,
+                     c.io.word, c.io.packets};
   const int64_t grid = grid_of(c.S, kEmitBlock);
+  // (an engine without the spectator endpoint poll launches the kernel it always did)
+  auto launch = [&](auto PC) {
+    constexpr int PP = decltype(PC)::value;
+    if (e->spoll.on) p2p_spec_emit_kernel<PP, true><<<grid, kEmitBlock, lds, e->stream>>>(p);
+    else p2p_spec_emit_kernel<PP, false><<<grid, kEmitBlock, lds, e->stream>>>(p);
+  };
   switch (e->cfg.num_players) {
-    case 1: p2p_spec_emit_kernel<1><<<grid, kEmitBlock, lds, e->stream>>>(p); break;
-    case 2: p2p_spec_emit_kernel<2><<<grid, kEmitBlock, lds, e->stream>>>(p); break;
-    case 3: p2p_spec_emit_kernel<3><<<grid, kEmitBlock, lds, e->stream>>>(p); break;
-    default: p2p_spec_emit_kernel<4><<<grid, kEmitBlock, lds, e->stream>>>(p); break;
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 3: launch(std::integral_constant<int, 3>{}); break;
+    default: launch(std::integral_constant<int, 4>{}); break;
   }
   return emit_end(e, e->spec, (size_t)e->spec_k, io, c, on_device);
 }

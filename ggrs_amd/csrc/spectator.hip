@@ -272,6 +272,7 @@ int ggrs_spectator_engine_destroy(ggrs_spectator_engine_t* e) {
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   spectator_ingest_free(e);
+  spectator_poll_free(e);
   e->timer.destroy();
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;

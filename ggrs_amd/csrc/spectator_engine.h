@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "poll_host.h"
 
 struct ggrs_spectator_engine {
   ggrs_spectator_config_t cfg{};
@@ -29,6 +30,8 @@ struct ggrs_spectator_engine {
   int32_t pkt_maxp = 0;            // the hosts' max_prediction
   ggrs::PacketFeedState feed;      // (last: the session's input window ends here; stop: the call whose packet
                                    // stopped the session; staged beside the packets: the calls' notes)
+  // the endpoint poll (ggrs_spectator_set_endpoint_poll, spectator_poll.hip): one endpoint per session
+  ggrs::PollHost poll;
 };
 
 namespace ggrs {
@@ -38,5 +41,7 @@ namespace ggrs {
 constexpr int32_t kSpecFeedStop = INT32_MIN;
 
 int spectator_ingest_free(ggrs_spectator_engine* e);
+// spectator_poll.hip: free the endpoint poll's buffers
+int spectator_poll_free(ggrs_spectator_engine* e);
 
 }  // namespace ggrs

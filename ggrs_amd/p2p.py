@@ -92,6 +92,9 @@ def _bind(L):
     L.ggrs_p2p_set_endpoint_poll.argtypes = [vp, u64, u64, u64]
     L.ggrs_p2p_poll_endpoints.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
     L.ggrs_p2p_read_endpoint_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ggrs_p2p_set_spectator_poll.argtypes = [vp, u64, u64, u64]
+    L.ggrs_p2p_poll_spectator_endpoints.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
+    L.ggrs_p2p_read_spectator_endpoint_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     for name in _lib.EXPORTS:
         if name.startswith("ggrs_p2p_"):
             getattr(L, name).restype = ctypes.c_int
@@ -536,6 +539,40 @@ class P2PEngine:
         S = self.num_sessions
         out = [np.zeros(S, np.int32)] + [np.zeros(S, np.uint64) for _ in range(4)] + [np.zeros(S, np.int32) for _ in range(2)]
         _lib.check(self._L.ggrs_p2p_read_endpoint_state(self._h, *(_vp(a) for a in out)))
+        return tuple(out)
+
+    # ---- spectator endpoint poll (include/ggrs_amd.h, "Spectator endpoint poll"; p2p_spec_poll.hip)
+    def set_spectator_poll(self, disconnect_timeout_ms=2000, disconnect_notify_start_ms=500, start_ms=0):
+        """The sessions' endpoints towards their spectators are polled on the device
+        (poll_spectator_endpoints): the 200 ms retry and quality-report timers, NetworkInterrupted /
+        NetworkResumed, the disconnect timeout and the way to Shutdown; after set_spectator_emit, before
+        the first call.  From then on emit_spectator_packets refuses a call not polled, and an endpoint
+        the poll closed gets nothing more."""
+        _lib.check(self._L.ggrs_p2p_set_spectator_poll(self._h, disconnect_timeout_ms, disconnect_notify_start_ms,
+                                                       start_ms))
+
+    def poll_spectator_endpoints(self, first_call, n_calls, now_ms, kinds=None, close_in=None, out=None):
+        """The polls of calls first_call .. first_call + n_calls - 1 (in order, each once): now_ms [n]
+        uint64 (never decreasing), kinds [n][K][S] uint8 (wire.unpack's per spectator link, None: nothing
+        arrived) and close_in [n][K][S] uint8 (the host's own disconnect_player(spectator), None).
+        Returns (resend, send_report, net_events) [n][K][S] uint8 as numpy arrays -- or, with out = such
+        a tuple of torch tensors on the engine's device (now_ms then an int64 device tensor holding the
+        u64's bits, kinds and close_in device tensors), fills and returns them; the launch runs on the
+        engine's stream.  resend is emit_spectator_packets' input."""
+        n, S, K = int(n_calls), self.num_sessions, getattr(self, "num_spectators", 1)
+        dev = out is not None
+        outs = list(out) if dev else [np.zeros((n, K, S), np.uint8) for _ in range(3)]
+        ptrs, keep = _lib.marshal([now_ms, kinds, close_in] + outs, ((n,),) + ((n, K, S),) * 5,
+                                  ("int64" if dev else "uint64",) + ("uint8",) * 5, dev)
+        _lib.check(self._L.ggrs_p2p_poll_spectator_endpoints(self._h, first_call, n, *ptrs, int(dev)))
+        return tuple(outs)
+
+    def spectator_endpoint_state(self):
+        """endpoint_state()'s tuple for the spectator endpoints, [K][S] each."""
+        S, K = self.num_sessions, getattr(self, "num_spectators", 1)
+        out = ([np.zeros((K, S), np.int32)] + [np.zeros((K, S), np.uint64) for _ in range(4)]
+               + [np.zeros((K, S), np.int32) for _ in range(2)])
+        _lib.check(self._L.ggrs_p2p_read_spectator_endpoint_state(self._h, *(_vp(a) for a in out)))
         return tuple(out)
 
     KERNEL_FORMS = {"default": 0, "unstaged": 1, "lockstep": 2, "flat": 3, "chains": 4, "flat_queues": 5,

@@ -61,6 +61,10 @@ def _bind(L):
     L.ggrs_spectator_set_packet_feed.argtypes = [vp, i32, i32, i32]
     L.ggrs_spectator_receive_packets.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32]
     L.ggrs_spectator_read_packet_results.argtypes = [vp, i32, i32, vp, vp]
+    u64 = ctypes.c_uint64
+    L.ggrs_spectator_set_endpoint_poll.argtypes = [vp, u64, u64, u64]
+    L.ggrs_spectator_poll_endpoints.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
+    L.ggrs_spectator_read_endpoint_state.argtypes = [vp, vp, vp, vp, vp, vp]
     for name in _lib.EXPORTS:
         if name.startswith("ggrs_spectator_"):
             getattr(L, name).restype = ctypes.c_int
@@ -166,6 +170,42 @@ class SpectatorEngine:
         ack = np.zeros((n_calls, self.num_sessions), np.int32)
         _lib.check(self._L.ggrs_spectator_read_packet_results(self._h, first_call, n_calls, _vp(status), _vp(ack)))
         return status, ack
+
+    # ---- endpoint poll (include/ggrs_amd.h, "Spectator engine: endpoint poll"; spectator_poll.hip)
+    def set_endpoint_poll(self, disconnect_timeout_ms=2000, disconnect_notify_start_ms=500, start_ms=0):
+        """Every session's host endpoint is polled on the device (poll_endpoints): when to acknowledge,
+        when a quality report is due, NetworkInterrupted / NetworkResumed and the one Disconnected;
+        before the first arrival and call.  The defaults are the reference's; every clock of the
+        endpoints starts at start_ms."""
+        _lib.check(self._L.ggrs_spectator_set_endpoint_poll(self._h, disconnect_timeout_ms, disconnect_notify_start_ms,
+                                                            start_ms))
+        self.disconnect_timeout_ms, self.disconnect_notify_start_ms = disconnect_timeout_ms, disconnect_notify_start_ms
+
+    def poll_endpoints(self, first_call, n_calls, now_ms, kinds=None, events=None, out=None):
+        """The polls of calls first_call .. first_call + n_calls - 1 (in order, each once; with the
+        packet feed after their packets were received): now_ms [n] uint64 (never decreasing), kinds
+        and events [n][S] uint8 (wire.unpack's; None: nothing arrived / no disconnect request).
+        Returns (send_ack, send_report, net_events) [n][S] uint8 as numpy arrays -- or, with out = such
+        a tuple of torch tensors on the engine's device (now_ms then an int64 device tensor holding the
+        u64's bits, kinds and events device tensors), fills and returns them; the launch runs on the
+        engine's stream (synchronize() before another stream reads).  net_events holds GGRS_NET_* bits;
+        the endpoint never leaves Running, so GGRS_NET_SHUTDOWN never appears."""
+        n, S = int(n_calls), self.num_sessions
+        dev = out is not None
+        outs = list(out) if dev else [np.zeros((n, S), np.uint8) for _ in range(3)]
+        ptrs, keep = _lib.marshal([now_ms, kinds, events] + outs, ((n,),) + ((n, S),) * 5,
+                                  ("int64" if dev else "uint64",) + ("uint8",) * 5, dev)
+        _lib.check(self._L.ggrs_spectator_poll_endpoints(self._h, first_call, n, *ptrs, int(dev)))
+        return tuple(outs)
+
+    def endpoint_state(self):
+        """(last_recv_ms, last_input_recv_ms, last_report_ms [S] uint64; flags [S] int32: bit 0
+        disconnect_notify_sent, bit 1 disconnect_event_sent; disconnected_call [S] int32: the call that
+        raised the one Disconnected, -1)."""
+        S = self.num_sessions
+        out = [np.zeros(S, np.uint64) for _ in range(3)] + [np.zeros(S, np.int32) for _ in range(2)]
+        _lib.check(self._L.ggrs_spectator_read_endpoint_state(self._h, *(_vp(a) for a in out)))
+        return tuple(out)
 
     def advance_frames(self, n=1):
         _lib.check(self._L.ggrs_spectator_advance_frames(self._h, n))

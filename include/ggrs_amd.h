@@ -965,8 +965,9 @@ int ggrs_p2p_read_desync_state(ggrs_p2p_engine_t* eng, int32_t* status, int32_t*
  * reference plays on.  The timeout ends that wait only if it comes first: keep input_capacity above the
  * calls that disconnect_timeout_ms spans, plus the calls queued ahead.  A session whose remote players
  * were all disconnected while its link was silent still holds that row: it stops input_capacity calls
- * after the silence began, so a server retires a timed-out match before then.  Not built: the spectator endpoints'
- * and the spectator engine's own poll(); NetworkStats::kbps_sent (it sums size_of_val(&Message), a Rust
+ * after the silence began, so a server retires a timed-out match before then.  The spectator endpoints'
+ * poll is "Spectator endpoint poll" below, the spectator engine's own "Spectator engine: endpoint poll".
+ * Not built: NetworkStats::kbps_sent (it sums size_of_val(&Message), a Rust
  * layout); MAX_EVENT_QUEUE_SIZE (the unit reports per call, the host forms GgrsEvents).
  * Kernel: p2p_poll.hip (the step: poll_device.h). */
 #define GGRS_NET_INTERRUPTED 1  /* Event::NetworkInterrupted at this call (its payload: disconnect_timeout - notify_start) */
@@ -1002,6 +1003,64 @@ int ggrs_p2p_poll_endpoints(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t 
 int ggrs_p2p_read_endpoint_state(ggrs_p2p_engine_t* eng, int32_t* state, uint64_t* last_recv_ms,
                                  uint64_t* last_input_recv_ms, uint64_t* last_report_ms, uint64_t* shutdown_ms,
                                  int32_t* flags, int32_t* closed_call);
+
+/* ---- Spectator endpoint poll: the same for the num_spectators endpoints a session has towards its
+ * spectators (ggrs_p2p_set_spectator_emit is their send side): P2PSession::poll_remote_clients'
+ * spectator loop (p2p_session.rs:458-464) with handle_event (:866-878), disconnect_player (:506-509)
+ * and disconnect_player_at_frame's spectator branch (:645-652), on the device.  Every array is
+ * [n][K][S], K = num_spectators; times, strictness and the start values are "Endpoint poll"'s.
+ * Endpoint k of session s at call c, at clock now = max(now_ms[c], the engine's last clock):
+ *  0. Shutdown: every output 0, nothing changes;
+ *  1. kinds[c][k] != 0: last_recv_time = now; GGRS_NET_RESUMED while Running with
+ *     disconnect_notify_sent set, the flag cleared.  A spectator sends no Input: an Input bit counts as a
+ *     message and nothing else, and there is no send_ack output.  Stated divergence: the reference would
+ *     decode it and then hit the assert! of p2p_session.rs:882;
+ *  2. ext has two sources: close_in[c][k] != 0, the host's own disconnect_player(spectator), which
+ *     raises no event; and spectator emit having closed this endpoint with GGRS_EMIT_DISCONNECTED at a
+ *     call before c -- the Event::Disconnected send_input queues (protocol.rs:443-445), which the
+ *     reference handles at the next poll, so GGRS_NET_DISCONNECTED is raised here.  Neither sets
+ *     disconnect_event_sent (the reference's paths do not);
+ *  3. while Running, in poll()'s order: (a) running_last_input_recv + 200 < now: resend[c][k] = 1 and
+ *     the time reset -- nothing else ever resets it for a spectator, so the retry recurs every time more
+ *     than 200 ms have passed; (b) send_report as in "Endpoint poll"; (c) GGRS_NET_INTERRUPTED; (d) with
+ *     disconnect_event_sent clear and last_recv_time + disconnect_timeout < now: GGRS_NET_DISCONNECTED,
+ *     the flag set, ext = 1; (e) ext: the state becomes Disconnected, shutdown_timeout = now + 5000,
+ *     closed_call = c;
+ *  4. Disconnected at entry: shutdown_timeout < now gives Shutdown and GGRS_NET_SHUTDOWN.
+ * A spectator's timeout does not enter the game: no events row is written, the session and its other
+ * endpoints are untouched.  What spectator emit reads: an endpoint whose closed_call is >= 0 and <= c
+ * pushes and emits nothing from call c on, a resend included; its emit status becomes GGRS_EMIT_CLOSED
+ * and its emit closing call the poll's (send_input's early return and the is_running() check,
+ * protocol.rs:426, p2p_session.rs:736).  With the unit on, ggrs_p2p_emit_spectator_packets returns
+ * GGRS_E_STATE, naming the call, for a call whose spectator endpoints were not polled; the order within
+ * a call is otherwise free, and no ordering against ggrs_p2p_advance_frames is needed.
+ * Stated limit: the overflow of step 2 is seen as of the launch.  It lands at the reference's call when
+ * each call's emit precedes the next call's poll (the live loop); polled further ahead, it lands at the
+ * next launch's first call.  At the reference's defaults the 2000 ms timeout precedes the 128-input
+ * overflow at 60 fps, so this is a backstop.  Everything else is independent of how the calls are split.
+ * No keep-alive row: see "Endpoint poll"; the argument does not depend on who the peer is.  Out of scope:
+ * NetworkStats (kbps_sent, send_queue_len), MAX_EVENT_QUEUE_SIZE, fixed-latency engines, peers'
+ * disconnect reports.  Measured (profiles/spectator_poll_rate.json): 0.67 us per call at K = 1 and
+ * 1.06 us at K = 4 for 65,536 sessions at 64 calls per launch; spectator emit with the unit on 1.8 % and
+ * 2.7 % slower than without.  Kernel: p2p_spec_poll.hip (the step and the launch loop: poll_device.h). */
+/* Part of the configuration: after ggrs_p2p_set_spectator_emit (GGRS_E_STATE without it, on a
+ * fixed-latency engine and after the first call; setting spectator emit again turns the unit off),
+ * disconnect_notify_start_ms > disconnect_timeout_ms is GGRS_E_INVALID. */
+int ggrs_p2p_set_spectator_poll(ggrs_p2p_engine_t* eng, uint64_t disconnect_timeout_ms,
+                                uint64_t disconnect_notify_start_ms, uint64_t start_ms);
+/* The polls of calls first_call .. first_call + n_calls - 1, in order, each exactly once
+ * (GGRS_E_INVALID otherwise, nothing launched).  now_ms [n] u64 as for ggrs_p2p_poll_endpoints: a host
+ * array that decreases is GGRS_E_INVALID, a device value below the engine's last clock is taken as that
+ * clock.  kinds and close_in [n][K][S] u8 (NULL: none); outputs resend (ggrs_p2p_emit_spectator_packets'
+ * input), send_report and net_events [n][K][S] u8, any may be NULL.  Host arrays are staged, device
+ * arrays (on_device) read and written in place on the engine's stream. */
+int ggrs_p2p_poll_spectator_endpoints(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, const uint64_t* now_ms,
+                                      const uint8_t* kinds, const uint8_t* close_in, uint8_t* resend,
+                                      uint8_t* send_report, uint8_t* net_events, int32_t on_device);
+/* Per endpoint, [K][S] each, as ggrs_p2p_read_endpoint_state.  Any pointer may be NULL. */
+int ggrs_p2p_read_spectator_endpoint_state(ggrs_p2p_engine_t* eng, int32_t* state, uint64_t* last_recv_ms,
+                                           uint64_t* last_input_recv_ms, uint64_t* last_report_ms,
+                                           uint64_t* shutdown_ms, int32_t* flags, int32_t* closed_call);
 
 /* ---------------------------------------------------------------------------------------------
  * Spectators: num_sessions independent SpectatorSessions (src/sessions/p2p_spectator_session.rs),
@@ -1141,6 +1200,54 @@ int ggrs_spectator_receive_packets(ggrs_spectator_engine_t* eng, int32_t first_c
  * stopping call); ack_frame = last_recv after the call (what send_input_ack carries). */
 int ggrs_spectator_read_packet_results(ggrs_spectator_engine_t* eng, int32_t first_call, int32_t n_calls,
                                        int32_t* status, int32_t* ack_frame);
+
+/* ---- Spectator engine: endpoint poll.  SpectatorSession::poll_remote_clients
+ * (p2p_spectator_session.rs:133-156) with handle_event (:199-239) over the host endpoint's
+ * UdpProtocol::poll (protocol.rs:329-376, :534-551, :569-574, :608, :634), per call, on the device:
+ * when to acknowledge, when a quality report is due, when the host went quiet (NetworkInterrupted /
+ * NetworkResumed) and when it is gone (GgrsEvent::Disconnected).  Times, strictness and the start
+ * values are "Endpoint poll"'s.  Call c at clock now = max(now_ms[c], the engine's last clock):
+ *  1. kinds[c] != 0: last_recv_time = now; with disconnect_notify_sent set, the flag is cleared and
+ *     GGRS_NET_RESUMED raised;
+ *  2. events[c] != 0 (an accepted Input carried disconnect_requested): with disconnect_event_sent clear,
+ *     GGRS_NET_DISCONNECTED is raised, the flag set and disconnected_call = c (on_input, :569-574);
+ *  3. decoded = kinds has the Input bit and, with the packet feed, the feed's status of call c is >= 0:
+ *     running_last_input_recv = now, send_ack[c] = 1;
+ *  4. poll(), in order: (a) the retry timer resets running_last_input_recv; it has no output, because a
+ *     spectator has nothing pending, and is kept so that the field equals the reference's; (b)
+ *     running_last_quality_report + 200 < now: send_report[c] = 1, the time set; (c)
+ *     GGRS_NET_INTERRUPTED as in "Endpoint poll"; (d) disconnect_event_sent clear and last_recv_time +
+ *     disconnect_timeout < now: GGRS_NET_DISCONNECTED, the flag set, disconnected_call = c.
+ * Where this differs from the P2P units: the reference's spectator never calls host.disconnect() --
+ * handle_event only forwards the event -- so the endpoint stays Running for good, its timers and the
+ * interrupted / resumed pair go on after the one Disconnected, and GGRS_NET_SHUTDOWN never appears.
+ * GGRS_NET_DISCONNECTED stands for both causes here (the spectator engine has no events row in which
+ * the requested one could be seen).  The poll changes nothing in the sessions: a spectator whose host is
+ * gone waits, as the reference's does.  No keep-alive row (see "Endpoint poll").  Out of scope:
+ * NetworkStats, MAX_EVENT_QUEUE_SIZE, the spectator's update_local_frame_advantage (protocol.rs:260-269:
+ * the report's frame_advantage stays the caller's input to ggrs_wire_pack), enacting anything on the
+ * sessions.  Measured (profiles/spectator_poll_rate.json): 0.65 us per call for 65,536 sessions at 64
+ * calls per launch.  Kernel: spectator_poll.hip (the step and the launch loop: poll_device.h). */
+/* Part of the configuration: GGRS_E_STATE after the first call or arrival;
+ * disconnect_notify_start_ms > disconnect_timeout_ms is GGRS_E_INVALID. */
+int ggrs_spectator_set_endpoint_poll(ggrs_spectator_engine_t* eng, uint64_t disconnect_timeout_ms,
+                                     uint64_t disconnect_notify_start_ms, uint64_t start_ms);
+/* The polls of calls first_call .. first_call + n_calls - 1: in call order, each exactly once; with the
+ * packet feed after the call's packets were received and while its status row is among the
+ * input_capacity rows held (GGRS_E_INVALID otherwise, nothing launched).  No ordering against
+ * ggrs_spectator_advance_frames.  now_ms [n] u64: a host array that decreases is GGRS_E_INVALID, a
+ * device value below the engine's last clock is taken as that clock.  kinds and events [n][S] u8 as
+ * ggrs_wire_unpack writes them (NULL: none); outputs send_ack, send_report (ggrs_wire_pack's) and
+ * net_events (GGRS_NET_* bits) [n][S] u8, any may be NULL.  Host arrays are staged, device arrays
+ * (on_device) read and written in place on the engine's stream.  The result does not depend on how the
+ * calls are split over invocations. */
+int ggrs_spectator_poll_endpoints(ggrs_spectator_engine_t* eng, int32_t first_call, int32_t n_calls,
+                                  const uint64_t* now_ms, const uint8_t* kinds, const uint8_t* events, uint8_t* send_ack,
+                                  uint8_t* send_report, uint8_t* net_events, int32_t on_device);
+/* Per session, [num_sessions] each: the three times, flags (bit 0 disconnect_notify_sent, bit 1
+ * disconnect_event_sent) and the call that raised the one Disconnected (-1).  Any pointer may be NULL. */
+int ggrs_spectator_read_endpoint_state(ggrs_spectator_engine_t* eng, uint64_t* last_recv_ms, uint64_t* last_input_recv_ms,
+                                       uint64_t* last_report_ms, int32_t* flags, int32_t* disconnected_call);
 
 /* ---- Input wire codec, batched (src/network/compression.rs:14-182; bitfield-rle 0.2.1 runs,
  * bincode 1.3 fixint framing of EncodedInputSequence).  Replaces compression::encode / decode as

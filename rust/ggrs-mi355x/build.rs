@@ -36,6 +36,8 @@ const UNITS: &[(&str, &[&str])] = &[
     ("p2p_desync.hip", NONE),
     ("wire.hip", NONE),
     ("p2p_poll.hip", NONE),
+    ("p2p_spec_poll.hip", NONE),
+    ("spectator_poll.hip", NONE),
 ];
 
 fn main() {

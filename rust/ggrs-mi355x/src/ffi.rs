@@ -510,6 +510,35 @@ extern "C" {
         flags: *mut i32,
         closed_call: *mut i32,
     ) -> i32;
+    // spectator endpoint poll (p2p_spec_poll.hip): the same for the sessions' endpoints towards their spectators
+    pub fn ggrs_p2p_set_spectator_poll(
+        eng: *mut ggrs_p2p_engine_t,
+        disconnect_timeout_ms: u64,
+        disconnect_notify_start_ms: u64,
+        start_ms: u64,
+    ) -> i32;
+    pub fn ggrs_p2p_poll_spectator_endpoints(
+        eng: *mut ggrs_p2p_engine_t,
+        first_call: i32,
+        n_calls: i32,
+        now_ms: *const u64,
+        kinds: *const u8,
+        close_in: *const u8,
+        resend: *mut u8,
+        send_report: *mut u8,
+        net_events: *mut u8,
+        on_device: i32,
+    ) -> i32;
+    pub fn ggrs_p2p_read_spectator_endpoint_state(
+        eng: *mut ggrs_p2p_engine_t,
+        state: *mut i32,
+        last_recv_ms: *mut u64,
+        last_input_recv_ms: *mut u64,
+        last_report_ms: *mut u64,
+        shutdown_ms: *mut u64,
+        flags: *mut i32,
+        closed_call: *mut i32,
+    ) -> i32;
 
     // ---- spectators (src/sessions/p2p_spectator_session.rs), batched
     pub fn ggrs_spectator_engine_create(cfg: *const ggrs_spectator_config_t, out: *mut *mut ggrs_spectator_engine_t) -> i32;
@@ -539,6 +568,15 @@ extern "C" {
                                           notes: *const i32, on_device: i32) -> i32;
     pub fn ggrs_spectator_read_packet_results(eng: *mut ggrs_spectator_engine_t, first_call: i32, n_calls: i32,
                                               status: *mut i32, ack_frame: *mut i32) -> i32;
+    // the spectators' endpoint poll (spectator_poll.hip): the host endpoint's timers and timeout per call
+    pub fn ggrs_spectator_set_endpoint_poll(eng: *mut ggrs_spectator_engine_t, disconnect_timeout_ms: u64,
+                                            disconnect_notify_start_ms: u64, start_ms: u64) -> i32;
+    pub fn ggrs_spectator_poll_endpoints(eng: *mut ggrs_spectator_engine_t, first_call: i32, n_calls: i32,
+                                         now_ms: *const u64, kinds: *const u8, events: *const u8, send_ack: *mut u8,
+                                         send_report: *mut u8, net_events: *mut u8, on_device: i32) -> i32;
+    pub fn ggrs_spectator_read_endpoint_state(eng: *mut ggrs_spectator_engine_t, last_recv_ms: *mut u64,
+                                              last_input_recv_ms: *mut u64, last_report_ms: *mut u64, flags: *mut i32,
+                                              disconnected_call: *mut i32) -> i32;
 
     // ---- input wire codec, batched (src/network/compression.rs:14-182); device pointers
     pub fn ggrs_codec_encode(ref_: *const u8, pending: *const u8, count: *const i32, n_packets: i64,
