@@ -90,5 +90,17 @@ __device__ inline void fletcher_entity_mod(uint32_t& s1d, uint32_t& s2d, const u
   s2d += rem255_doubled(mad_u24(c_e, a2, kJ2Bias) - j2);
 }
 
+// checksum of one frame from the block's sums of doubled per-entity remainders (t1d, t2d: even,
+// < 510 N) plus the frame counter at byte offset 0 (sum1 += A_f, sum2 += n A_f - B_f)
+__device__ inline uint16_t finish_checksum(uint32_t t1d, uint32_t t2d, int32_t frame, int32_t N) {
+  const uint64_t n = 4 + (uint64_t)kEntityBytes * N;
+  const uint32_t fw = (uint32_t)frame;
+  const uint32_t a = __builtin_amdgcn_udot4(fw, 0x01010101u, 0u, false);
+  const uint32_t b = __builtin_amdgcn_udot4(fw, 0x03020100u, 0u, false);  // <= 1530
+  const uint64_t t1 = (uint64_t)(t1d >> 1) + a;
+  const uint64_t t2 = (uint64_t)(t2d >> 1) + n * a + 1530u - b;  // + 6 * 255 keeps it >= 0
+  return (uint16_t)(((t2 % 255u) << 8) | (t1 % 255u));
+}
+
 }  // namespace particles
 }  // namespace ggrs
