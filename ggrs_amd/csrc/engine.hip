@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "engine.h"
+#include "synctest_save.h"
 
 #pragma clang fp contract(off)
 
@@ -241,7 +242,7 @@ __global__ __launch_bounds__(256) void restore_kernel(CheckpointMap m, const uin
 
 // Every store of the v4 kernel is a buffer store whose offset is pushed out of the descriptor's
 // range on lanes that must not store (no exec-mask branches); buffers must be < 1 GiB.
-constexpr uint32_t kOob = 0x40000000u;  // >= every descriptor's num_records; two of them never wrap
+constexpr uint32_t kOob = kSaveOob;  // 2^30: >= every descriptor's num_records; two of them never wrap
 
 __device__ inline __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
@@ -607,9 +608,12 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v4_kernel(PipeParams
 // is one dependent issue chain with nothing to hide its latencies behind, so the core blocks are
 // split by function over two waves: wave 0 (the producer) runs the whole flow above but in a core
 // step only advances, rotates and hands every lane's post-advance state over in LDS; wave 1 (the
-// consumer) takes part in the core blocks only and does their saves -- Fletcher sums, first-seen
-// compare, stores -- and their batch, one block behind the producer.  One LDS-only workgroup
-// barrier per 8-step block, two hand-off buffers.
+// consumer) takes part in the core blocks only and does their saves and their batch, one block
+// behind the producer.  In a core step every role holds the post-advance state of the same frame,
+// so the consumer saves once per step, not once per role (synctest_save.h): it compares the roles'
+// states bit for bit, then lane (session, role j, player) checksums and stores step j's cell --
+// one Fletcher pass and seven stores per block; a difference fails the launch as a checksum
+// mismatch does.  One LDS-only workgroup barrier per 8-step block, two hand-off buffers.
 // v5 step kinds: std::false_type the general step (raw input, per-step domain test, stores only for
 // the launch's chains), std::true_type the core step, EdgeStep the core step's arithmetic for the
 // launch's first and last steps (some roles hold chains of other launches: their stores write the
@@ -657,7 +661,8 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   // block each.  A step's slot holds every lane's post-advance state (fields 0..3 as one uint4 per
   // lane, then field 4 as one word per lane); lds_hrec holds, per buffer and lane, the InputRec
   // the lane's batch sub-step needs (lds_raw is re-read while the consumer still works).
-  constexpr int kHSlot = kWave * 20;
+  constexpr int kHSlot = kSaveHandSlot;
+  static_assert(!kSplit || (P == kSavePlayers && CD == kSaveCd && kB == kSaveCd), "synctest_save.h is the split kernel's block");
   __shared__ __attribute__((aligned(16))) uint8_t lds_hand[kSplit ? 2 * kB * kHSlot : 16];
   __shared__ uint4 lds_hrec[kSplit ? 2 * kWave : 1];
   __shared__ int32_t lds_ctl[2];  // split kernel: the number of core blocks and their first step
@@ -1063,8 +1068,9 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   int32_t t = p.f0;
   if constexpr (kSplit) {
     if (consumer) {
-      // The consumer wave: per core block, the saves of its eight steps (checksum, first-seen
-      // compare in the same step, the seven stores) and its batch, from the producer's hand-off.
+      // The consumer wave: per core block, its saves (synctest_save.h: the roles' states compared
+      // bit for bit, then one checksum and one save per step, lane (session, role j, player)
+      // taking step j -- seven stores) and its batch, from the producer's hand-off.
       block_barrier();  // the producer's publish()
       const int32_t nb = lds_ctl[0];
       t = lds_ctl[1];
@@ -1073,16 +1079,11 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
       sr = __builtin_amdgcn_readfirstlane((g0 + 1 + (t - p.f0)) % R);
       sb = __builtin_amdgcn_readfirstlane(p.trace_cap ? (p.f0 - (CD - 1) + (t - p.f0)) % p.trace_cap : 0);
       const uint32_t hand_first = (uint32_t)(base + (CD - 1) * Pp + pl);  // role cd-1's lane: the stash
+      const SaveLane save = make_save_lane(valid, pl, s, L, ck_base, first_base);
+      const uint64_t save_lanes = __ballot(valid);
       for (int32_t k = 0; k < nb; ++k, t += kB) {
         block_barrier();  // block k's hand-off buffer is written
         const uint8_t* hb = lds_hand + (k & 1) * (kB * kHSlot);
-        uint32_t v[kB][5];
-#pragma unroll
-        for (int u = 0; u < kB; u++) {
-          const uint4 a = *reinterpret_cast<const uint4*>(hb + u * kHSlot + wl * 16);
-          v[u][0] = a.x, v[u][1] = a.y, v[u][2] = a.z, v[u][3] = a.w;
-          v[u][4] = *reinterpret_cast<const uint32_t*>(hb + u * kHSlot + kWave * 16 + wl * 4);
-        }
         uint32_t bv[5];
         {
           const uint8_t* st = hb + (j & (kB - 1)) * kHSlot;
@@ -1091,17 +1092,10 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
           bv[4] = *reinterpret_cast<const uint32_t*>(st + kWave * 16 + hand_first * 4);
         }
         const uint4 brec = lds_hrec[(k & 1) * kWave + wl];
-#pragma unroll
-        for (int u = 0; u < kB; u++) {
-          const uint32_t frame1 = (uint32_t)(t + u - CD + 1);
-          const uint32_t ck = cell_checksum(v[u], frame1);
-          acc |= ck ^ first_seen(ck);
-          store_cell(v[u], frame1, ck, (uint32_t)sr);
-          sr = sr + 1 == R ? 0 : sr + 1;
-        }
+        bad |= synctest_save_block(hb, save, rs_ring, R, (uint32_t)sr, t, wl, j, save_lanes);
+        sr = sr + kB >= R ? sr + kB - R : sr + kB;  // R > 8
         batch_run(std::true_type(), t, kB, bv, brec);
       }
-      bad |= __ballot(acc != 0) & cmp_lanes;
       if (bad && wl == __builtin_ctzll(bad)) atomicCAS(p.fail_f0, -1, p.f0);
       // Every store of this wave has reached memory before the producer passes the last barrier:
       // its last steps write ring cells (steps t and t + R share one), trace cells and cur after
@@ -1172,8 +1166,9 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
     pend_lanes = cmp_lanes;
     glibc_sincosf_domain_raw(__builtin_bit_cast(float, w[4]), &sc_s, &sc_c, &sc_qs, &sc_qc);
     // the producer is one dependent chain: it issues first when both waves of a SIMD are ready,
-    // the consumer fills the cycles it leaves (measured, DESIGN.md §5: 0.154 -> 0.146 ms; stamped
-    // per role, the producer then waits a quarter of each block at the barrier for the consumer)
+    // the consumer fills the cycles it leaves (measured, DESIGN.md §5: 0.154 -> 0.146 ms with the
+    // per-role saves; with one save per step, where the consumer is the shorter wave, 0.131 ->
+    // 0.115 ms)
     if constexpr (kSplit) __builtin_amdgcn_s_setprio(1);
     for (int32_t k = 0; k < n_core; ++k, t += kB) {
       // Block k's records were read during block k - 1, ahead of its barrier (whose lgkmcnt(0)
@@ -1315,7 +1310,9 @@ int v4_sessions_per_block(const ggrs_engine* e) {
 }
 
 int v5_sessions_per_block(const ggrs_engine* e) {
-  if (e->cfg.check_distance != 8 || !pipe_buffers_fit(e)) return 0;
+  // (R > 8: a core block's eight saves go to eight ring slots -- synctest_save.h; always so, since
+  // check_distance < max_prediction = R - 1)
+  if (e->cfg.check_distance != 8 || e->R <= 8 || !pipe_buffers_fit(e)) return 0;
   return kWave / (8 * e->Pp);
 }
 
