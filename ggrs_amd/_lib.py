@@ -29,6 +29,13 @@ GGRS_DESYNC_ROW_LOST = -21  # ggrs_p2p_read_desync_state's status
 # ggrs_p2p_poll_endpoints' net_events bits and ggrs_p2p_read_endpoint_state's state
 GGRS_NET_INTERRUPTED, GGRS_NET_RESUMED, GGRS_NET_DISCONNECTED, GGRS_NET_SHUTDOWN = 1, 2, 4, 8
 GGRS_ENDPOINT_RUNNING, GGRS_ENDPOINT_DISCONNECTED, GGRS_ENDPOINT_SHUTDOWN = 0, 1, 2
+# the event queue's record kinds (ggrs_event_record_t.kind) and ggrs_p2p_read_event_queue_state's status
+(GGRS_EVENT_DISCONNECTED, GGRS_EVENT_NETWORK_INTERRUPTED, GGRS_EVENT_NETWORK_RESUMED, GGRS_EVENT_WAIT_RECOMMENDATION,
+ GGRS_EVENT_DESYNC_DETECTED) = 1, 2, 3, 4, 5
+GGRS_EVENTS_LOST = -27
+# ggrs_event_record_t: 16 bytes; a drained list adds the session in front
+EVENT_RECORD = np.dtype([("kind", "u1"), ("endpoint", "u1"), ("reserved", "<u2"), ("call", "<i4"), ("payload", "<u8")])
+DRAINED_EVENT = np.dtype([("session", "<i4")] + [(n, EVENT_RECORD.fields[n][0]) for n in EVENT_RECORD.names])
 # ggrs_wire_unpack's slot_status codes (accepted: tag + 1, empty: 0)
 GGRS_WIRE_E_BINCODE, GGRS_WIRE_E_SHAPE, GGRS_WIRE_E_CAP, GGRS_WIRE_E_CLOCK, GGRS_WIRE_E_RANGE = -22, -23, -24, -25, -26
 NULL_FRAME = -1
@@ -78,6 +85,7 @@ EXPORTS = (
     "ggrs_p2p_compare_reports", "ggrs_p2p_read_desync_events", "ggrs_p2p_read_desync_state",
     "ggrs_p2p_set_endpoint_poll", "ggrs_p2p_poll_endpoints", "ggrs_p2p_read_endpoint_state",
     "ggrs_p2p_set_spectator_poll", "ggrs_p2p_poll_spectator_endpoints", "ggrs_p2p_read_spectator_endpoint_state",
+    "ggrs_p2p_set_event_queue", "ggrs_p2p_collect_events", "ggrs_p2p_drain_events", "ggrs_p2p_read_event_queue_state",
     "ggrs_spectator_engine_create", "ggrs_spectator_engine_destroy", "ggrs_spectator_engine_config",
     "ggrs_spectator_add_inputs", "ggrs_spectator_add_arrivals", "ggrs_spectator_advance_frames",
     "ggrs_spectator_calls", "ggrs_spectator_synchronize", "ggrs_spectator_read_sessions",
@@ -85,6 +93,8 @@ EXPORTS = (
     "ggrs_spectator_timing_reset", "ggrs_spectator_timing_stop", "ggrs_spectator_timing_read",
     "ggrs_spectator_set_packet_feed", "ggrs_spectator_receive_packets", "ggrs_spectator_read_packet_results",
     "ggrs_spectator_set_endpoint_poll", "ggrs_spectator_poll_endpoints", "ggrs_spectator_read_endpoint_state",
+    "ggrs_spectator_set_event_queue", "ggrs_spectator_collect_events", "ggrs_spectator_drain_events",
+    "ggrs_spectator_read_event_queue_state",
     "ggrs_codec_encode", "ggrs_codec_decode", "ggrs_codec_encode_chunked", "ggrs_codec_decode_chunked", "ggrs_codec_max_packet_bytes", "ggrs_codec_set_direct",
     "ggrs_wire_max_datagram_bytes", "ggrs_wire_unpack", "ggrs_wire_pack",
 )
@@ -219,6 +229,35 @@ def marshal(arrays, shapes, dtypes, device):
             keep.append(a)
             args.append(ctypes.c_void_p(a.ctypes.data))
     return args, keep
+
+
+def drain_events(fn, handle, max_records, out=None):
+    """ggrs_*_drain_events: (events, n_left).  events is a DRAINED_EVENT array of the records read --
+    or, with out = (session int32 [max_records], records uint8 [max_records][16]) torch tensors on the
+    engine's device, the count of records written to them."""
+    n_read, n_left = ctypes.c_int32(), ctypes.c_int32()
+    m = int(max_records)
+    if out is not None:
+        ptrs, _ = marshal(out, ((m,), (m, 16)), ("int32", "uint8"), True)
+        check(fn(handle, m, *ptrs, ctypes.byref(n_read), ctypes.byref(n_left), 1))
+        return n_read.value, n_left.value
+    sess, recs = np.zeros(m, np.int32), np.zeros(m, EVENT_RECORD)
+    check(fn(handle, m, ctypes.c_void_p(sess.ctypes.data), ctypes.c_void_p(recs.ctypes.data), ctypes.byref(n_read),
+             ctypes.byref(n_left), 0))
+    ev = np.zeros(n_read.value, DRAINED_EVENT)
+    ev["session"] = sess[:n_read.value]
+    for name in EVENT_RECORD.names:
+        ev[name] = recs[name][:n_read.value]
+    return ev, n_left.value
+
+
+def event_queue_state(fn, handle, num_sessions, capacity, queue=True):
+    """ggrs_*_read_event_queue_state: (length, dropped, status, closed_call) [S] int32 each and, with
+    queue, the queues [capacity][S] as EVENT_RECORD in queue order (zero past a queue's length)."""
+    out = [np.zeros(num_sessions, np.int32) for _ in range(4)]
+    q = np.zeros((capacity, num_sessions), EVENT_RECORD) if queue else None
+    check(fn(handle, *(ctypes.c_void_p(a.ctypes.data) for a in out), ctypes.c_void_p(q.ctypes.data) if queue else None))
+    return tuple(out) + ((q,) if queue else ())
 
 
 def check(rc):

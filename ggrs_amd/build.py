@@ -19,12 +19,13 @@ LIB = os.path.join(HERE, "libggrs_amd.so")
 UNITS = ("engine.hip", "requests.hip", "branch.hip", "particles.hip", "p2p.hip", "p2p_sched.hip", "codec.hip",
          "lane_encode.cpp", "spectator.hip", "p2p_ingest.hip", "p2p_emit.hip", "spectator_ingest.hip",
          "p2p_spec_emit.hip", "p2p_time_sync.hip", "p2p_desync.hip", "wire.hip", "p2p_poll.hip",
-         "p2p_spec_poll.hip", "spectator_poll.hip")
+         "p2p_spec_poll.hip", "spectator_poll.hip", "p2p_events.hip", "spectator_events.hip")
 SOURCES = [os.path.join(CSRC, f) for f in UNITS]
 HEADERS = [os.path.join(CSRC, h) for h in ("box_game.h", "glibc_sincosf.h", "common.h", "particles.h", "p2p_engine.h",
                                            "engine.h", "host_device.h", "p2p_plan.h", "codec_device.h", "emit_device.h",
                                            "ingest_device.h", "p2p_device.h", "spectator_engine.h", "wire_device.h",
-                                           "poll_device.h", "poll_host.h", "synctest_save.h")] + [
+                                           "poll_device.h", "poll_host.h", "synctest_save.h",
+                                           "events_device.h", "events_host.h")] + [
     os.path.join(ROOT, "include", "ggrs_amd.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

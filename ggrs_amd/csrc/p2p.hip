@@ -1530,6 +1530,7 @@ int ggrs_p2p_engine_destroy(ggrs_p2p_engine_t* e) {
   p2p_ingest_free(e);
   p2p_poll_free(e);
   p2p_spec_poll_free(e);
+  p2p_events_free(e);
   p2p_desync_free(e);
   p2p_time_sync_free(e);
   p2p_spec_emit_free(e);

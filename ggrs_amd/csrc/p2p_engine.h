@@ -4,7 +4,7 @@
 // scheduled mode) and p2p_emit.hip (its send side) and p2p_spec_emit.hip (the send side towards the
 // sessions' spectators), p2p_time_sync.hip and p2p_desync.hip (time sync and the checksum comparison,
 // which walk the same calls by the same order rule) and p2p_poll.hip (the endpoint poll, which walks the
-// calls before they run), with the host side the two send sides share (PacketEmitState: configuration
+// calls before they run) and p2p_events.hip (the sessions' event queues), with the host side the two send sides share (PacketEmitState: configuration
 // and call-order checks, the staging of a launch's arrays, the group plan; emit_begin / emit_end: an
 // emit call before and after the unit's kernel launch; EmitCalls: what emit_begin hands the unit for
 // its kernel's parameters).  Host code and plain structs only; no kernels here.
@@ -17,6 +17,7 @@
 
 #include "codec_device.h"
 #include "common.h"
+#include "events_host.h"
 #include "p2p_plan.h"
 #include "poll_host.h"
 
@@ -261,6 +262,9 @@ struct ggrs_p2p_engine {
   // endpoints a session has towards its spectators, [..][spec_k][S] rows; spectator emit reads its
   // closed_call row
   ggrs::PollHost spoll;
+  // event queue (ggrs_p2p_set_event_queue; p2p_events.hip): every session's GgrsEvent queue, filled per call
+  // from the polls', time sync's and the comparison's outputs, drained into one list
+  ggrs::EventQueueHost evq;
   ggrs::SpanTimer timer;
 };
 
@@ -325,6 +329,8 @@ enum DcField : int {
   kDcFirstRemote,
   kDcFields
 };
+// p2p_events.hip: free the event queue's buffers
+int p2p_events_free(ggrs_p2p_engine* e);
 // p2p_poll.hip: free the endpoint poll's buffers
 int p2p_poll_free(ggrs_p2p_engine* e);
 // p2p_spec_poll.hip: free the spectator endpoint poll's buffers (and turn it off)

@@ -273,6 +273,7 @@ int ggrs_spectator_engine_destroy(ggrs_spectator_engine_t* e) {
     if (b) (void)hipFree(b);
   spectator_ingest_free(e);
   spectator_poll_free(e);
+  spectator_events_free(e);
   e->timer.destroy();
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "events_host.h"
 #include "poll_host.h"
 
 struct ggrs_spectator_engine {
@@ -32,6 +33,8 @@ struct ggrs_spectator_engine {
                                    // stopped the session; staged beside the packets: the calls' notes)
   // the endpoint poll (ggrs_spectator_set_endpoint_poll, spectator_poll.hip): one endpoint per session
   ggrs::PollHost poll;
+  // the event queue (ggrs_spectator_set_event_queue, spectator_events.hip): every session's GgrsEvent queue
+  ggrs::EventQueueHost evq;
 };
 
 namespace ggrs {
@@ -43,5 +46,7 @@ constexpr int32_t kSpecFeedStop = INT32_MIN;
 int spectator_ingest_free(ggrs_spectator_engine* e);
 // spectator_poll.hip: free the endpoint poll's buffers
 int spectator_poll_free(ggrs_spectator_engine* e);
+// spectator_events.hip: free the event queue's buffers
+int spectator_events_free(ggrs_spectator_engine* e);
 
 }  // namespace ggrs

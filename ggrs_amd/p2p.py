@@ -95,6 +95,10 @@ def _bind(L):
     L.ggrs_p2p_set_spectator_poll.argtypes = [vp, u64, u64, u64]
     L.ggrs_p2p_poll_spectator_endpoints.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
     L.ggrs_p2p_read_spectator_endpoint_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ggrs_p2p_set_event_queue.argtypes = [vp, i32]
+    L.ggrs_p2p_collect_events.argtypes = [vp, i32, i32] + [vp] * 6 + [i32] + [vp] * 5 + [i32]
+    L.ggrs_p2p_drain_events.argtypes = [vp, i32, vp, vp, P(i32), P(i32), i32]
+    L.ggrs_p2p_read_event_queue_state.argtypes = [vp, vp, vp, vp, vp, vp]
     for name in _lib.EXPORTS:
         if name.startswith("ggrs_p2p_"):
             getattr(L, name).restype = ctypes.c_int
@@ -574,6 +578,52 @@ class P2PEngine:
                + [np.zeros((K, S), np.int32) for _ in range(2)])
         _lib.check(self._L.ggrs_p2p_read_spectator_endpoint_state(self._h, *(_vp(a) for a in out)))
         return tuple(out)
+
+    # ---- event queue (include/ggrs_amd.h, "Event queue"; p2p_events.hip)
+    def set_event_queue(self, capacity=128):
+        """Every session's GgrsEvent queue is kept on the device (collect_events, drain_events): a ring
+        of `capacity` (128..1024) records per session; after set_arrival_schedule, before the first
+        call."""
+        _lib.check(self._L.ggrs_p2p_set_event_queue(self._h, capacity))
+        self.event_capacity = capacity
+
+    def collect_events(self, first_call, n_calls, events=None, disc_req=None, handled_inputs=None, net_events=None,
+                       spec_net_events=None, skip_frames=None, desync=None, on_device=False):
+        """What calls first_call .. first_call + n_calls - 1 (in order, each once) push into the
+        sessions' event queues, with the reference's trim to 100: events, disc_req, handled_inputs and
+        net_events [n][S] uint8, spec_net_events [n][K][S] uint8, skip_frames [n][S] int32, any None
+        (nothing happened).  desync: None, the tuple desync_events() returns (call, session, frame
+        int32, local, remote uint16), or "engine" for the records compare_reports appended on the
+        device.  on_device: every array is a torch tensor on the engine's device (uint16 as int16)."""
+        n, S, K = int(n_calls), self.num_sessions, getattr(self, "num_spectators", 0)
+        own = isinstance(desync, str)
+        if own and desync != "engine":
+            raise _lib.InvalidRequest(-1, 'desync is None, a tuple of five arrays or "engine"')
+        ds = (None,) * 5 if own or desync is None else tuple(desync)
+        nd = -1 if own else (0 if desync is None else int(ds[0].shape[0]))
+        if nd == 0:
+            ds = (None,) * 5
+        u16 = "int16" if on_device else "uint16"
+        ptrs, keep = _lib.marshal([events, disc_req, handled_inputs, net_events, spec_net_events, skip_frames, *ds],
+                                  ((n, S),) * 4 + ((n, K, S), (n, S)) + ((max(nd, 0),),) * 5,
+                                  ("uint8",) * 5 + ("int32",) * 4 + (u16, u16), on_device)
+        _lib.check(self._L.ggrs_p2p_collect_events(self._h, first_call, n, *ptrs[:6], nd, *ptrs[6:], int(bool(on_device))))
+
+    def drain_events(self, max_records=None, out=None):
+        """Every session's events() at once -> (events, n_left): a structured array (_lib.DRAINED_EVENT:
+        session, kind, endpoint, reserved, call, payload) ordered by session, then queue order; those
+        queues are left empty.  With max_records too small, whole sessions in ascending order while
+        they fit; n_left records stay queued.  out: see _lib.drain_events."""
+        if max_records is None:
+            max_records = self.num_sessions * getattr(self, "event_capacity", 0)
+        return _lib.drain_events(self._L.ggrs_p2p_drain_events, self._h, max_records, out)
+
+    def event_queue_state(self, queue=True):
+        """(length, dropped, status, closed_call) [S] int32 each -- status 0 or GGRS_EVENTS_LOST,
+        closed_call the call that closed the remote endpoint (-1) -- and, with queue, the queues
+        [capacity][S] (_lib.EVENT_RECORD) in queue order, without draining."""
+        return _lib.event_queue_state(self._L.ggrs_p2p_read_event_queue_state, self._h, self.num_sessions,
+                                      getattr(self, "event_capacity", 0), queue)
 
     KERNEL_FORMS = {"default": 0, "unstaged": 1, "lockstep": 2, "flat": 3, "chains": 4, "flat_queues": 5,
                     "canonical": 6}

@@ -65,6 +65,10 @@ def _bind(L):
     L.ggrs_spectator_set_endpoint_poll.argtypes = [vp, u64, u64, u64]
     L.ggrs_spectator_poll_endpoints.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
     L.ggrs_spectator_read_endpoint_state.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ggrs_spectator_set_event_queue.argtypes = [vp, i32]
+    L.ggrs_spectator_collect_events.argtypes = [vp, i32, i32, vp, vp, i32]
+    L.ggrs_spectator_drain_events.argtypes = [vp, i32, vp, vp, P(i32), P(i32), i32]
+    L.ggrs_spectator_read_event_queue_state.argtypes = [vp, vp, vp, vp, vp, vp]
     for name in _lib.EXPORTS:
         if name.startswith("ggrs_spectator_"):
             getattr(L, name).restype = ctypes.c_int
@@ -206,6 +210,34 @@ class SpectatorEngine:
         out = [np.zeros(S, np.uint64) for _ in range(3)] + [np.zeros(S, np.int32) for _ in range(2)]
         _lib.check(self._L.ggrs_spectator_read_endpoint_state(self._h, *(_vp(a) for a in out)))
         return tuple(out)
+
+    # ---- event queue (include/ggrs_amd.h, "Spectator engine: event queue"; spectator_events.hip)
+    def set_event_queue(self, capacity=128):
+        """Every session's GgrsEvent queue is kept on the device (collect_events, drain_events): a ring
+        of `capacity` (128..1024) records per session; before the first arrival and call."""
+        _lib.check(self._L.ggrs_spectator_set_event_queue(self._h, capacity))
+        self.event_capacity = capacity
+
+    def collect_events(self, first_call, n_calls, handled_inputs=None, net_events=None, on_device=False):
+        """What calls first_call .. first_call + n_calls - 1 (in order, each once) push into the
+        sessions' event queues: net_events [n][S] uint8 (poll_endpoints') and handled_inputs [n][S]
+        uint8 (the call decoded a new frame), either None.  Every push and every handled Input trims
+        the queue to 100.  on_device: torch tensors on the engine's device."""
+        n, S = int(n_calls), self.num_sessions
+        ptrs, keep = _lib.marshal([handled_inputs, net_events], ((n, S),) * 2, ("uint8",) * 2, on_device)
+        _lib.check(self._L.ggrs_spectator_collect_events(self._h, first_call, n, *ptrs, int(bool(on_device))))
+
+    def drain_events(self, max_records=None, out=None):
+        """Every session's events() at once -> (events, n_left), as P2PEngine.drain_events."""
+        if max_records is None:
+            max_records = self.num_sessions * getattr(self, "event_capacity", 0)
+        return _lib.drain_events(self._L.ggrs_spectator_drain_events, self._h, max_records, out)
+
+    def event_queue_state(self, queue=True):
+        """(length, dropped, status, closed_call) [S] int32 each -- closed_call the call that pushed the
+        one Disconnected (-1) -- and, with queue, the queues [capacity][S] in queue order."""
+        return _lib.event_queue_state(self._L.ggrs_spectator_read_event_queue_state, self._h, self.num_sessions,
+                                      getattr(self, "event_capacity", 0), queue)
 
     def advance_frames(self, n=1):
         _lib.check(self._L.ggrs_spectator_advance_frames(self._h, n))

@@ -968,7 +968,8 @@ int ggrs_p2p_read_desync_state(ggrs_p2p_engine_t* eng, int32_t* status, int32_t*
  * after the silence began, so a server retires a timed-out match before then.  The spectator endpoints'
  * poll is "Spectator endpoint poll" below, the spectator engine's own "Spectator engine: endpoint poll".
  * Not built: NetworkStats::kbps_sent (it sums size_of_val(&Message), a Rust
- * layout); MAX_EVENT_QUEUE_SIZE (the unit reports per call, the host forms GgrsEvents).
+ * layout).  The unit reports per call; the sessions' GgrsEvent queues with MAX_EVENT_QUEUE_SIZE are
+ * "Event queue" below, which takes the net_events row.
  * Kernel: p2p_poll.hip (the step: poll_device.h). */
 #define GGRS_NET_INTERRUPTED 1  /* Event::NetworkInterrupted at this call (its payload: disconnect_timeout - notify_start) */
 #define GGRS_NET_RESUMED 2      /* Event::NetworkResumed */
@@ -1039,8 +1040,9 @@ int ggrs_p2p_read_endpoint_state(ggrs_p2p_engine_t* eng, int32_t* state, uint64_
  * next launch's first call.  At the reference's defaults the 2000 ms timeout precedes the 128-input
  * overflow at 60 fps, so this is a backstop.  Everything else is independent of how the calls are split.
  * No keep-alive row: see "Endpoint poll"; the argument does not depend on who the peer is.  Out of scope:
- * NetworkStats (kbps_sent, send_queue_len), MAX_EVENT_QUEUE_SIZE, fixed-latency engines, peers'
- * disconnect reports.  Measured (profiles/spectator_poll_rate.json): 0.67 us per call at K = 1 and
+ * NetworkStats (kbps_sent, send_queue_len), fixed-latency engines, peers' disconnect reports (the
+ * GgrsEvent queue with MAX_EVENT_QUEUE_SIZE is "Event queue" below, which takes the net_events rows).
+ * Measured (profiles/spectator_poll_rate.json): 0.67 us per call at K = 1 and
  * 1.06 us at K = 4 for 65,536 sessions at 64 calls per launch; spectator emit with the unit on 1.8 % and
  * 2.7 % slower than without.  Kernel: p2p_spec_poll.hip (the step and the launch loop: poll_device.h). */
 /* Part of the configuration: after ggrs_p2p_set_spectator_emit (GGRS_E_STATE without it, on a
@@ -1061,6 +1063,104 @@ int ggrs_p2p_poll_spectator_endpoints(ggrs_p2p_engine_t* eng, int32_t first_call
 int ggrs_p2p_read_spectator_endpoint_state(ggrs_p2p_engine_t* eng, int32_t* state, uint64_t* last_recv_ms,
                                            uint64_t* last_input_recv_ms, uint64_t* last_report_ms,
                                            uint64_t* shutdown_ms, int32_t* flags, int32_t* closed_call);
+
+/* ---- Event queue: every session's P2PSession::event_queue (p2p_session.rs:149) on the device, filled per
+ * call from the rows the other units wrote, and P2PSession::events() (:573-576) for all sessions in one
+ * call: a drain into one dense list.  Arrival-schedule mode is required; every other unit combines with
+ * it, and none is required: the unit is a function of the rows it is given.  Per session a ring of
+ * `capacity` 16-byte records (ggrs_event_record_t), head and length, a `closed` flag for the endpoint
+ * towards the remote players (one endpoint per session holds them all, as in packet emit) and a counter
+ * `dropped`, all empty / open / 0 at first.  A record: kind (GGRS_EVENT_*; no Synchronizing /
+ * Synchronized kinds, which no code of the reference raises), endpoint (0: the remote players'
+ * endpoint, 1 + k: spectator endpoint k -- it stands in for GgrsEvent's addr), the call that pushed it
+ * and a 64-bit payload: NetworkInterrupted disconnect_timeout - disconnect_notify_start in ms
+ * (protocol.rs:353-356; of ggrs_p2p_set_endpoint_poll for endpoint 0, of ggrs_p2p_set_spectator_poll for
+ * the others, 0 without that unit), WaitRecommendation skip_frames, DesyncDetected frame |
+ * (uint64_t)(local_checksum | remote_checksum << 16) << 32, else 0.
+ * Call c, in advance_frame's order (:265-357):
+ *  a. poll_remote_clients (:430-469) with handle_event (:846-902).  The remote endpoint first, in this
+ *     order: GGRS_NET_RESUMED in net_events[c] pushes NetworkResumed; disc_req[c] != 0 (an accepted Input
+ *     carried disconnect_requested: on_input's Event::Disconnected, protocol.rs:569-574, which the
+ *     endpoint poll's rows do not hold) pushes Disconnected while the endpoint is open;
+ *     GGRS_NET_INTERRUPTED pushes NetworkInterrupted; GGRS_NET_DISCONNECTED pushes Disconnected while the
+ *     endpoint is open.  The endpoint closes (closed_call = c) with disc_req[c] != 0, with a remote
+ *     player's bit in events[c] -- the host's own disconnect_player closes it without an event
+ *     (:485-511, protocol.rs:311-319) -- and with a pushed Disconnected, in that order, so a disconnect
+ *     request after the host's own disconnect and a timeout after a request raise nothing (the endpoint
+ *     poll raises no GGRS_NET_DISCONNECTED for such an endpoint; the rule shows with hand-made rows
+ *     only).  GGRS_NET_SHUTDOWN is no GgrsEvent.  Then spectator endpoints k = 0 .. K - 1 in ascending
+ *     order (the reference walks a HashMap), K = num_spectators of ggrs_p2p_set_spectator_emit or 0:
+ *     NetworkResumed, NetworkInterrupted, Disconnected from spec_net_events[c][k].  After every push, and
+ *     once if handled_inputs[c] != 0 (the endpoint decoded at least one new frame: an Event::Input was
+ *     handled, which pushes nothing), the oldest events go while more than 100 are queued
+ *     (MAX_EVENT_QUEUE_SIZE, the end of every handle_event, :898-901);
+ *  b. compare_local_checksums_against_peers (:904-937): the call's DesyncDetected records in ascending
+ *     frame order, no trim;
+ *  c. check_wait_recommendation (:804-817): skip_frames[c] > 0 pushes WaitRecommendation, no trim.
+ * The queue may therefore hold more than 100 events between two endpoint events, as the reference's
+ * does.  Stated divergences: the reference's VecDeque grows, here a push into a full ring drops the
+ * oldest record and counts it in `dropped`; the rows cannot tell two reference orders apart in one case
+ * -- a spectator's overflow Disconnected, queued by the previous call's send_input, against a Resumed of
+ * the same poll -- and the fixed order above holds.
+ * The desync records of an invocation are a list in no order; the order a session needs comes from the
+ * keys (call, then frame, then the checksums).  A session takes at most 64 records from one invocation
+ * (two calls' worth of the 32 reports one call can compare); with more it keeps 64 of them (which is
+ * unspecified), its status becomes GGRS_EVENTS_LOST for good, and the other sessions go on.  A record
+ * naming a call outside the invocation's or a session outside the engine's is passed over.
+ * Out of scope: enacting a WaitRecommendation, several remote endpoints per session, fixed-latency
+ * engines, peers' disconnect reports, a desync list that was full (ggrs_p2p_set_desync_compare's
+ * max_events is the caller's to size).
+ * Measured (profiles/event_queue_rate.json; 65,536 sessions, 64 calls per launch, a live server's event
+ * density): collect 2.90 us per call at K = 0 and 4.01 us at K = 4, 3.8x and 5.3x the endpoint poll of the
+ * same calls (0.76 us); a drain of one launch's 174,105 records takes 160 us of host time around the call.
+ * Kernels: p2p_events.hip (the step, the collect loop and the drain: events_device.h). */
+typedef struct ggrs_event_record {
+  uint8_t kind;      /* GGRS_EVENT_* */
+  uint8_t endpoint;  /* 0 the remote players' endpoint (a spectator's host), 1 + k spectator endpoint k */
+  uint16_t reserved; /* 0 */
+  int32_t call;      /* the call that pushed the record */
+  uint64_t payload;
+} ggrs_event_record_t;
+#define GGRS_EVENT_DISCONNECTED 1
+#define GGRS_EVENT_NETWORK_INTERRUPTED 2
+#define GGRS_EVENT_NETWORK_RESUMED 3
+#define GGRS_EVENT_WAIT_RECOMMENDATION 4
+#define GGRS_EVENT_DESYNC_DETECTED 5
+#define GGRS_EVENTS_LOST (-27)  /* a session had more desync records in one invocation than it can take */
+/* Part of the configuration (after ggrs_p2p_set_arrival_schedule(eng, 1), before the first call):
+ * capacity in 128..1024 records per session (GGRS_E_INVALID otherwise).  GGRS_E_STATE after the first
+ * call and on a fixed-latency engine. */
+int ggrs_p2p_set_event_queue(ggrs_p2p_engine_t* eng, int32_t capacity);
+/* Steps a-c for calls first_call .. first_call + n_calls - 1: in order, each exactly once
+ * (GGRS_E_INVALID otherwise, nothing launched); no ordering against ggrs_p2p_advance_frames.  Rows, any
+ * may be NULL (nothing happened): events (the calls' events bytes), disc_req, handled_inputs and
+ * net_events (ggrs_p2p_poll_endpoints') [n][S] u8, spec_net_events (ggrs_p2p_poll_spectator_endpoints')
+ * [n][K][S] u8, skip_frames (ggrs_p2p_time_sync's) [n][S] i32.  The desync records: n_desync of them in
+ * ds_call, ds_session, ds_frame, ds_local, ds_remote, as ggrs_p2p_read_desync_events returns them; or
+ * n_desync == -1 with the five NULL: the engine's own list, the records ggrs_p2p_compare_reports
+ * appended -- GGRS_E_STATE, naming the call, unless the comparison has run through call first_call +
+ * n_calls - 1.  on_device as ggrs_p2p_emit_packets (every array then a device array, read on the
+ * engine's stream).  The result does not depend on how the calls are split over invocations
+ * (GGRS_EVENTS_LOST does: its bound is per invocation).  GGRS_E_STATE without ggrs_p2p_set_event_queue. */
+int ggrs_p2p_collect_events(ggrs_p2p_engine_t* eng, int32_t first_call, int32_t n_calls, const uint8_t* events,
+                            const uint8_t* disc_req, const uint8_t* handled_inputs, const uint8_t* net_events,
+                            const uint8_t* spec_net_events, const int32_t* skip_frames, int32_t n_desync,
+                            const int32_t* ds_call, const int32_t* ds_session, const int32_t* ds_frame,
+                            const uint16_t* ds_local, const uint16_t* ds_remote, int32_t on_device);
+/* Every session's events() at once: the queues of sessions 0, 1, .. in that order, each in queue order,
+ * as one dense list -- session [max_records] i32 and records [max_records] -- and those queues left
+ * empty.  With max_records too small whole sessions are drained in ascending order while they fit; the
+ * first session that does not fit and all later ones keep their queues.  n_read: the records written,
+ * n_left: the records still queued (host values, either may be NULL; the call waits for its launches).
+ * on_device != 0: session and records are device arrays (records 16-byte aligned), written on the
+ * engine's stream. */
+int ggrs_p2p_drain_events(ggrs_p2p_engine_t* eng, int32_t max_records, int32_t* session, ggrs_event_record_t* records,
+                          int32_t* n_read, int32_t* n_left, int32_t on_device);
+/* Without draining, per session [num_sessions] i32 each: the queue's length, the records a full ring
+ * dropped, the status (0, GGRS_EVENTS_LOST), the call that closed the remote endpoint (-1: open); queue
+ * [capacity][num_sessions] records in queue order, zero past the length.  Any pointer may be NULL. */
+int ggrs_p2p_read_event_queue_state(ggrs_p2p_engine_t* eng, int32_t* length, int32_t* dropped, int32_t* status,
+                                    int32_t* closed_call, ggrs_event_record_t* queue);
 
 /* ---------------------------------------------------------------------------------------------
  * Spectators: num_sessions independent SpectatorSessions (src/sessions/p2p_spectator_session.rs),
@@ -1224,9 +1324,10 @@ int ggrs_spectator_read_packet_results(ggrs_spectator_engine_t* eng, int32_t fir
  * GGRS_NET_DISCONNECTED stands for both causes here (the spectator engine has no events row in which
  * the requested one could be seen).  The poll changes nothing in the sessions: a spectator whose host is
  * gone waits, as the reference's does.  No keep-alive row (see "Endpoint poll").  Out of scope:
- * NetworkStats, MAX_EVENT_QUEUE_SIZE, the spectator's update_local_frame_advantage (protocol.rs:260-269:
+ * NetworkStats, the spectator's update_local_frame_advantage (protocol.rs:260-269:
  * the report's frame_advantage stays the caller's input to ggrs_wire_pack), enacting anything on the
- * sessions.  Measured (profiles/spectator_poll_rate.json): 0.65 us per call for 65,536 sessions at 64
+ * sessions (the GgrsEvent queue with MAX_EVENT_QUEUE_SIZE is "Spectator engine: event queue" below).
+ * Measured (profiles/spectator_poll_rate.json): 0.65 us per call for 65,536 sessions at 64
  * calls per launch.  Kernel: spectator_poll.hip (the step and the launch loop: poll_device.h). */
 /* Part of the configuration: GGRS_E_STATE after the first call or arrival;
  * disconnect_notify_start_ms > disconnect_timeout_ms is GGRS_E_INVALID. */
@@ -1248,6 +1349,29 @@ int ggrs_spectator_poll_endpoints(ggrs_spectator_engine_t* eng, int32_t first_ca
  * disconnect_event_sent) and the call that raised the one Disconnected (-1).  Any pointer may be NULL. */
 int ggrs_spectator_read_endpoint_state(ggrs_spectator_engine_t* eng, uint64_t* last_recv_ms, uint64_t* last_input_recv_ms,
                                        uint64_t* last_report_ms, int32_t* flags, int32_t* disconnected_call);
+
+/* ---- Spectator engine: event queue.  SpectatorSession::handle_event (p2p_spectator_session.rs:199-239)
+ * over the endpoint poll's net_events row, kept per session on the device, and events() for all
+ * sessions in one call.  Step a of "Event queue" alone, for the session's one host endpoint (endpoint 0):
+ * NetworkResumed, NetworkInterrupted (payload: ggrs_spectator_set_endpoint_poll's disconnect_timeout -
+ * disconnect_notify_start, 0 without it), Disconnected -- GGRS_NET_DISCONNECTED already stands for both
+ * causes here, and it is pushed once (closed_call).  Every push and every handled Input
+ * (handled_inputs[c] != 0) trims, so a queue never holds more than 100 events; status stays 0.  The
+ * ring, `dropped`, the drain and the read-back are the P2P unit's; its own speed has not been
+ * measured (the collect loop is the P2P unit's without its second half).  Kernels: spectator_events.hip (events_device.h). */
+/* Part of the configuration: GGRS_E_STATE after the first call or arrival; capacity in 128..1024
+ * (GGRS_E_INVALID otherwise). */
+int ggrs_spectator_set_event_queue(ggrs_spectator_engine_t* eng, int32_t capacity);
+/* Calls first_call .. first_call + n_calls - 1, in order, each exactly once (GGRS_E_INVALID otherwise,
+ * nothing launched): handled_inputs and net_events [n][S] u8, either may be NULL.  on_device: device
+ * arrays, read on the engine's stream.  The result does not depend on how the calls are split. */
+int ggrs_spectator_collect_events(ggrs_spectator_engine_t* eng, int32_t first_call, int32_t n_calls,
+                                  const uint8_t* handled_inputs, const uint8_t* net_events, int32_t on_device);
+/* As ggrs_p2p_drain_events and ggrs_p2p_read_event_queue_state. */
+int ggrs_spectator_drain_events(ggrs_spectator_engine_t* eng, int32_t max_records, int32_t* session,
+                                ggrs_event_record_t* records, int32_t* n_read, int32_t* n_left, int32_t on_device);
+int ggrs_spectator_read_event_queue_state(ggrs_spectator_engine_t* eng, int32_t* length, int32_t* dropped,
+                                          int32_t* status, int32_t* closed_call, ggrs_event_record_t* queue);
 
 /* ---- Input wire codec, batched (src/network/compression.rs:14-182; bitfield-rle 0.2.1 runs,
  * bincode 1.3 fixint framing of EncodedInputSequence).  Replaces compression::encode / decode as

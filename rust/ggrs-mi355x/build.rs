@@ -38,6 +38,8 @@ const UNITS: &[(&str, &[&str])] = &[
     ("p2p_poll.hip", NONE),
     ("p2p_spec_poll.hip", NONE),
     ("spectator_poll.hip", NONE),
+    ("p2p_events.hip", NONE),
+    ("spectator_events.hip", NONE),
 ];
 
 fn main() {

@@ -78,6 +78,24 @@ pub const GGRS_WIRE_E_SHAPE: i32 = -23;
 pub const GGRS_WIRE_E_CAP: i32 = -24;
 pub const GGRS_WIRE_E_CLOCK: i32 = -25;
 pub const GGRS_WIRE_E_RANGE: i32 = -26;
+// event queue: ggrs_event_record_t's kinds and ggrs_p2p_read_event_queue_state's status
+pub const GGRS_EVENT_DISCONNECTED: i32 = 1;
+pub const GGRS_EVENT_NETWORK_INTERRUPTED: i32 = 2;
+pub const GGRS_EVENT_NETWORK_RESUMED: i32 = 3;
+pub const GGRS_EVENT_WAIT_RECOMMENDATION: i32 = 4;
+pub const GGRS_EVENT_DESYNC_DETECTED: i32 = 5;
+pub const GGRS_EVENTS_LOST: i32 = -27;
+
+/// One queued GgrsEvent (p2p_events.hip, spectator_events.hip): 16 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct ggrs_event_record_t {
+    pub kind: u8,
+    pub endpoint: u8,
+    pub reserved: u16,
+    pub call: i32,
+    pub payload: u64,
+}
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -539,6 +557,43 @@ extern "C" {
         flags: *mut i32,
         closed_call: *mut i32,
     ) -> i32;
+    // event queue (p2p_events.hip): every session's GgrsEvent queue on the device, drained in one call
+    pub fn ggrs_p2p_set_event_queue(eng: *mut ggrs_p2p_engine_t, capacity: i32) -> i32;
+    pub fn ggrs_p2p_collect_events(
+        eng: *mut ggrs_p2p_engine_t,
+        first_call: i32,
+        n_calls: i32,
+        events: *const u8,
+        disc_req: *const u8,
+        handled_inputs: *const u8,
+        net_events: *const u8,
+        spec_net_events: *const u8,
+        skip_frames: *const i32,
+        n_desync: i32,
+        ds_call: *const i32,
+        ds_session: *const i32,
+        ds_frame: *const i32,
+        ds_local: *const u16,
+        ds_remote: *const u16,
+        on_device: i32,
+    ) -> i32;
+    pub fn ggrs_p2p_drain_events(
+        eng: *mut ggrs_p2p_engine_t,
+        max_records: i32,
+        session: *mut i32,
+        records: *mut ggrs_event_record_t,
+        n_read: *mut i32,
+        n_left: *mut i32,
+        on_device: i32,
+    ) -> i32;
+    pub fn ggrs_p2p_read_event_queue_state(
+        eng: *mut ggrs_p2p_engine_t,
+        length: *mut i32,
+        dropped: *mut i32,
+        status: *mut i32,
+        closed_call: *mut i32,
+        queue: *mut ggrs_event_record_t,
+    ) -> i32;
 
     // ---- spectators (src/sessions/p2p_spectator_session.rs), batched
     pub fn ggrs_spectator_engine_create(cfg: *const ggrs_spectator_config_t, out: *mut *mut ggrs_spectator_engine_t) -> i32;
@@ -577,6 +632,16 @@ extern "C" {
     pub fn ggrs_spectator_read_endpoint_state(eng: *mut ggrs_spectator_engine_t, last_recv_ms: *mut u64,
                                               last_input_recv_ms: *mut u64, last_report_ms: *mut u64, flags: *mut i32,
                                               disconnected_call: *mut i32) -> i32;
+    // the spectators' event queue (spectator_events.hip)
+    pub fn ggrs_spectator_set_event_queue(eng: *mut ggrs_spectator_engine_t, capacity: i32) -> i32;
+    pub fn ggrs_spectator_collect_events(eng: *mut ggrs_spectator_engine_t, first_call: i32, n_calls: i32,
+                                         handled_inputs: *const u8, net_events: *const u8, on_device: i32) -> i32;
+    pub fn ggrs_spectator_drain_events(eng: *mut ggrs_spectator_engine_t, max_records: i32, session: *mut i32,
+                                       records: *mut ggrs_event_record_t, n_read: *mut i32, n_left: *mut i32,
+                                       on_device: i32) -> i32;
+    pub fn ggrs_spectator_read_event_queue_state(eng: *mut ggrs_spectator_engine_t, length: *mut i32, dropped: *mut i32,
+                                                 status: *mut i32, closed_call: *mut i32,
+                                                 queue: *mut ggrs_event_record_t) -> i32;
 
     // ---- input wire codec, batched (src/network/compression.rs:14-182); device pointers
     pub fn ggrs_codec_encode(ref_: *const u8, pending: *const u8, count: *const i32, n_packets: i64,
