@@ -24,7 +24,7 @@ SOURCES = [os.path.join(CSRC, f) for f in UNITS]
 HEADERS = [os.path.join(CSRC, h) for h in ("box_game.h", "glibc_sincosf.h", "common.h", "particles.h", "p2p_engine.h",
                                            "engine.h", "host_device.h", "p2p_plan.h", "codec_device.h", "emit_device.h",
                                            "ingest_device.h", "p2p_device.h", "spectator_engine.h", "wire_device.h",
-                                           "poll_device.h", "poll_host.h", "synctest_save.h",
+                                           "poll_device.h", "poll_host.h", "synctest_save.h", "synctest_sincos_block.h",
                                            "events_device.h", "events_host.h")] + [
     os.path.join(ROOT, "include", "ggrs_amd.h")]
 

@@ -324,9 +324,11 @@ __device__ inline void advance_player_rec(float& x, float& y, float& vx, float& 
 // after the multiplication (RN(k * -v) == -RN(k * v) exactly): (d & keep) ^ (sgn ^ (q & keep)).
 // KATs against the oracle: test_gpu_step_forms.py::test_step_form[rec_q-*], and test_chain with the
 // next step's raw sin/cos computed in the hook.
-template <typename Hook = NoHook>
-__device__ inline void advance_player_rec_q(float& x, float& y, float& vx, float& vy, float& rot, const InputRec& in,
-                                            float sr, float cr, uint32_t qs, uint32_t qc, Hook&& hook = Hook()) {
+// One text for both forms below: kTurn false leaves out the turn and the hook (rot is not read).
+template <bool kTurn, typename Hook>
+__device__ __forceinline__ void advance_player_rec_q_body(float& x, float& y, float& vx, float& vy, float& rot,
+                                                          const InputRec& in, float sr, float cr, uint32_t qs,
+                                                          uint32_t qc, Hook&& hook) {
   ggrs_f2 vel = ggrs_f2{vx, vy} * kFriction;
   const ggrs_f2 d = ggrs_f2{cr, sr} * kMovementSpeed;
   const float dx = d.x, dy = d.y;
@@ -334,9 +336,11 @@ __device__ inline void advance_player_rec_q(float& x, float& y, float& vx, float
   const uint32_t ix = (__builtin_bit_cast(uint32_t, dx) & in.keep) ^ wx;
   const uint32_t iy = (__builtin_bit_cast(uint32_t, dy) & in.keep) ^ wy;
   vel = vel + ggrs_f2{__builtin_bit_cast(float, ix), __builtin_bit_cast(float, iy)};
-  const float a = rot + __builtin_bit_cast(float, in.delta);
-  rot = a + (a < 0.0f ? kTwoPi : (a >= __builtin_bit_cast(float, in.thr) ? -kTwoPi : 0.0f));
-  hook(rot);
+  if constexpr (kTurn) {
+    const float a = rot + __builtin_bit_cast(float, in.delta);
+    rot = a + (a < 0.0f ? kTwoPi : (a >= __builtin_bit_cast(float, in.thr) ? -kTwoPi : 0.0f));
+    hook(rot);
+  }
   const ggrs_f2 sq = vel * vel;
   const float mag2 = sq.x + sq.y;
   const bool clamp = mag2 > kMaxSpeed * kMaxSpeed;
@@ -353,6 +357,20 @@ __device__ inline void advance_player_rec_q(float& x, float& y, float& vx, float
   y = __builtin_amdgcn_fmed3f(pos.y, 0.0f, kWindowHeight);
   vx = vel.x;
   vy = vel.y;
+}
+template <typename Hook = NoHook>
+__device__ inline void advance_player_rec_q(float& x, float& y, float& vx, float& vy, float& rot, const InputRec& in,
+                                            float sr, float cr, uint32_t qs, uint32_t qc, Hook&& hook = Hook()) {
+  advance_player_rec_q_body<true>(x, y, vx, vy, rot, in, sr, cr, qs, qc, hook);
+}
+// advance_player_rec_q without its turn: position and velocity only, for a caller that turns rot
+// itself with the same two f32 operations (synctest_sincos_block.h, block_rot_chain: the turn reads
+// rot, delta and thr only, and nothing else in the step reads rot).  sr, cr, qs, qc belong to the
+// rot the step starts from, as in advance_player_rec_q.
+__device__ inline void advance_player_rec_q_turned(float& x, float& y, float& vx, float& vy, const InputRec& in,
+                                                   float sr, float cr, uint32_t qs, uint32_t qc) {
+  float rot = 0.0f;
+  advance_player_rec_q_body<false>(x, y, vx, vy, rot, in, sr, cr, qs, qc, NoHook());
 }
 
 __device__ inline void advance_player_lean(float& x, float& y, float& vx, float& vy, float& rot,

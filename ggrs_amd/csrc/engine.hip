@@ -28,6 +28,7 @@
 #include "common.h"
 #include "engine.h"
 #include "synctest_save.h"
+#include "synctest_sincos_block.h"
 
 #pragma clang fp contract(off)
 
@@ -607,9 +608,15 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v4_kernel(PipeParams
 // kSplit (two players): 128 threads per block, the same sessions per block.  A lone wave per SIMD
 // is one dependent issue chain with nothing to hide its latencies behind, so the core blocks are
 // split by function over two waves: wave 0 (the producer) runs the whole flow above but in a core
-// step only advances, rotates and hands every lane's post-advance state over in LDS; wave 1 (the
-// consumer) takes part in the core blocks only and does their saves and their batch, one block
-// behind the producer.  In a core step every role holds the post-advance state of the same frame,
+// step only advances, rotates and hands every lane's post-advance state over in LDS -- and of the
+// advance, the eight turns of a block and their sin/cos are taken out of the steps: rot evolves
+// from rot and the step's InputRec alone, all eight records are in registers at the block's head,
+// so every lane runs the block's eight turns there and the lane of role j evaluates the sin/cos of
+// the rot after step j, once, into a 16-byte LDS entry that step j + 1 reads on every lane
+// (synctest_sincos_block.h: one f64 polynomial pass per block instead of eight); wave 1 (the
+// consumer) takes part in the core blocks only and does their saves and their batch (whose sin/cos
+// is the lane's own entry of the block), one block behind the producer.
+// In a core step every role holds the post-advance state of the same frame,
 // so the consumer saves once per step, not once per role (synctest_save.h): it compares the roles'
 // states bit for bit, then lane (session, role j, player) checksums and stores step j's cell --
 // one Fletcher pass and seven stores per block; a difference fails the launch as a checksum
@@ -665,6 +672,10 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   static_assert(!kSplit || (P == kSavePlayers && CD == kSaveCd && kB == kSaveCd), "synctest_save.h is the split kernel's block");
   __shared__ __attribute__((aligned(16))) uint8_t lds_hand[kSplit ? 2 * kB * kHSlot : 16];
   __shared__ uint4 lds_hrec[kSplit ? 2 * kWave : 1];
+  // Split kernel: the sin/cos entries of a core block (synctest_sincos_block.h), one per lane,
+  // double-buffered with the hand-off: the producer writes block k's at the head of block k and
+  // reads them in its steps, the consumer reads its own lane's for block k's batch.
+  __shared__ __attribute__((aligned(16))) uint8_t lds_sc[kSplit ? 2 * kSincosBlockBytes : 16];
   __shared__ int32_t lds_ctl[2];  // split kernel: the number of core blocks and their first step
   const int wl = threadIdx.x & (kWave - 1);
   // wave 0 produces, wave 1 consumes (one-wave kernel: the only wave does both).  Measured
@@ -880,7 +891,8 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   uint32_t acc = 0;
   const uint32_t in_at = (uint32_t)in_lane;
   // core steps: sin/cos of the rot each lane holds at the step's start, computed one step ahead
-  // (inside the previous step, from the rotated rot, before its speed clamp)
+  // (inside the previous step, from the rotated rot, before its speed clamp; in the split kernel's
+  // core blocks read from the block's entries, synctest_sincos_block.h)
   float sc_s = 0.0f, sc_c = 0.0f;  // the raw polynomial values (glibc_sincosf_domain_raw)
   uint32_t sc_qs = 0u, sc_qc = 0u;   // and their quadrant signs
 
@@ -919,8 +931,8 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
     if constexpr (!kMergedCk) __builtin_amdgcn_raw_buffer_store_b16((uint16_t)ck, rs_ring, co_first, cso, 0);
   };
   // core steps take the staged InputRec, non-core steps the raw input byte.  slot_off: the step's
-  // stash slot; in the split kernel's core steps (the producer's half of the step: the advance, the
-  // rotation and the hand-off) the step's hand-off slot
+  // stash slot.  (The split kernel's core steps are split_core_step below; its edge and general
+  // steps run here.)
   auto step = [&](auto core_tag, int32_t t, auto in, uint32_t slot_off) {
     constexpr bool kCore = decltype(core_tag)::value;
     constexpr bool kEdge = IsEdge<decltype(core_tag)>::value;
@@ -961,13 +973,8 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
 #pragma unroll
       for (int q = 0; q < 5; q++) nx[q] = (uint32_t)__builtin_amdgcn_ds_bpermute(src_rot, (int)w[q]);
     }
-    if constexpr (kSplit && kCore && !kEdge) {
-      // every lane's post-advance state to the consumer, which checksums, compares and stores it
-      // and runs the block's batch from the role cd-1 entries (the caller advances sr)
-      uint8_t* st = lds_hand + slot_off;
-      *reinterpret_cast<uint4*>(st + wl * 16) = make_uint4(w[0], w[1], w[2], w[3]);
-      *reinterpret_cast<uint32_t*>(st + kWave * 16 + wl * 4) = w[4];
-    } else {
+    static_assert(!(kSplit && kCore && !kEdge), "the split kernel's core steps are split_core_step");
+    {
       // role cd-1's post-advance state for the batch (every other lane writes the dump)
       {
         uint8_t* st = lds_stash + stash_w + slot_off;
@@ -994,11 +1001,31 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
       w[q] = Pp == 2 ? (uint32_t)__builtin_amdgcn_update_dpp((int)w[q], (int)w[q], 0x112, 0xF, 0xF, false) : nx[q];
   };
 
+  // The split kernel's core step (the producer's half): position and velocity from the sin/cos of
+  // the rot the step starts from, the hand-off of fields 0..3 (every lane's post-advance state goes
+  // to the consumer, which compares, checksums and stores it and runs the block's batch from the
+  // role cd-1 entries) and their role rotation.  rot is not here: the block's turns, their sin/cos
+  // and the hand-off's field 4 are the block's pass (synctest_sincos_block.h), and w[4] is the
+  // lane's own rot at the block's head.
+  auto split_core_step = [&](const uint4 in, uint32_t slot_off) {
+    float x = __builtin_bit_cast(float, w[0]), y = __builtin_bit_cast(float, w[1]);
+    float vx = __builtin_bit_cast(float, w[2]), vy = __builtin_bit_cast(float, w[3]);
+    advance_player_rec_q_turned(x, y, vx, vy, rec_of(in), sc_s, sc_c, sc_qs, sc_qc);
+    w[0] = __builtin_bit_cast(uint32_t, x);
+    w[1] = __builtin_bit_cast(uint32_t, y);
+    w[2] = __builtin_bit_cast(uint32_t, vx);
+    w[3] = __builtin_bit_cast(uint32_t, vy);
+    *reinterpret_cast<uint4*>(lds_hand + slot_off + wl * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+#pragma unroll
+    for (int q = 0; q < 4; q++) w[q] = (uint32_t)__builtin_amdgcn_update_dpp((int)w[q], (int)w[q], 0x112, 0xF, 0xF, false);
+  };
+
   // The batch over the stashes of steps tb .. tb + count - 1 (count <= 8; tb - f0 a multiple of
   // 8): role j < count advances step tb + j's stash -- chain cb = tb + j - (cd - 1), its frame cb,
   // with input cb, which step tb + j + 1 reads -- and stores the display checksum of frame cb + 1.
   // batch_run: the sub-step itself, from the stashed state v and the input `in` (core: the
   // InputRec, else the raw byte); batch: the one-wave form, which reads both from this wave's LDS.
+  uint4 batch_sc = make_uint4(0u, 0u, 0u, 0u);  // split kernel's consumer: the lane's sin/cos entry of the block
   auto batch_run = [&](auto core_tag, int32_t tb, int count, uint32_t(&v)[5], auto in) {
     constexpr bool kCore = decltype(core_tag)::value;
     constexpr bool kEdge = IsEdge<decltype(core_tag)>::value;
@@ -1011,7 +1038,14 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
       if constexpr (kCore) {
         float bs, bc;
         uint32_t bqs, bqc;
-        glibc_sincosf_domain_raw(rot, &bs, &bc, &bqs, &bqc);
+        if constexpr (kSplit && !kEdge) {
+          // the consumer's batch: rot is the rot of hand-off slot j, r[j] of the block, whose
+          // sin/cos this lane's own entry holds (synctest_sincos_block.h)
+          bs = __builtin_bit_cast(float, batch_sc.x), bc = __builtin_bit_cast(float, batch_sc.y);
+          bqs = batch_sc.z, bqc = batch_sc.w;
+        } else {
+          glibc_sincosf_domain_raw(rot, &bs, &bc, &bqs, &bqc);
+        }
         advance_player_rec_q(x, y, vx, vy, rot, rec_of(in), bs, bc, bqs, bqc);
       } else {
         advance_player(x, y, vx, vy, rot, (uint32_t)in);
@@ -1092,6 +1126,7 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
           bv[4] = *reinterpret_cast<const uint32_t*>(st + kWave * 16 + hand_first * 4);
         }
         const uint4 brec = lds_hrec[(k & 1) * kWave + wl];
+        batch_sc = *reinterpret_cast<const uint4*>(lds_sc + (k & 1) * kSincosBlockBytes + wl * kSincosEntry);
         bad |= synctest_save_block(hb, save, rs_ring, R, (uint32_t)sr, t, wl, j, save_lanes);
         sr = sr + kB >= R ? sr + kB - R : sr + kB;  // R > 8
         batch_run(std::true_type(), t, kB, bv, brec);
@@ -1191,9 +1226,33 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
       // block k over.
       const uint32_t slot0 = kSplit ? (uint32_t)(k & 1) * (kB * kHSlot) : 0u;
       if constexpr (kSplit) lds_hrec[(k & 1) * kWave + wl] = ahead[kB];
+      // Split kernel: the block's eight turns and its one sin/cos pass (synctest_sincos_block.h),
+      // from this lane's own rot and the block's records.  Step 0 runs on the sin/cos carried in
+      // registers (the previous block's entry of role 7, before the first block the evaluation
+      // above), step u > 0 on the entry of role u - 1, read one step ahead.
+      const uint8_t* scb = lds_sc + (kSplit ? (k & 1) * kSincosBlockBytes : 0);
+      uint4 sc_next = make_uint4(0u, 0u, 0u, 0u);
+      if constexpr (kSplit) {
+        const InputRec recs[kB] = {rec_of(ahead[0]), rec_of(ahead[1]), rec_of(ahead[2]), rec_of(ahead[3]),
+                                   rec_of(ahead[4]), rec_of(ahead[5]), rec_of(ahead[6]), rec_of(ahead[7])};
+        float rr[kB];
+        block_rot_chain(__builtin_bit_cast(float, w[4]), recs, rr);
+        sincos_block_pass(lds_hand + slot0, lds_sc + (k & 1) * kSincosBlockBytes, wl, j, rr);
+        w[4] = __builtin_bit_cast(uint32_t, rr[kB - 1]);
+      }
 #pragma unroll
       for (int u = 0; u < kB; u++) {
-        step(std::true_type(), t + u, ahead[u], slot0 + (uint32_t)(u * (kSplit ? kHSlot : kSlot)));
+        if constexpr (kSplit) {
+          if (u > 0) {
+            sc_s = __builtin_bit_cast(float, sc_next.x), sc_c = __builtin_bit_cast(float, sc_next.y);
+            sc_qs = sc_next.z, sc_qc = sc_next.w;
+          }
+          if (u == 0) wave_lds_sync();  // the entries are written
+          sc_next = sincos_block_entry(scb, wl, j, u);
+          split_core_step(ahead[u], slot0 + (uint32_t)(u * kHSlot));
+        } else {
+          step(std::true_type(), t + u, ahead[u], slot0 + (uint32_t)(u * kSlot));
+        }
         if (u < kB - 1) ahead[u] = tab_rec(b[u]);
         if (u == kAheadAt) {
           last = tab_rec(b[kB - 1]);
@@ -1202,6 +1261,9 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
       }
       ahead[kB - 1] = last;
       if constexpr (kSplit) {
+        // role 7's entry: the next block's step 0 (after the last core block, the edge block's)
+        sc_s = __builtin_bit_cast(float, sc_next.x), sc_c = __builtin_bit_cast(float, sc_next.y);
+        sc_qs = sc_next.z, sc_qc = sc_next.w;
         sb = sb + sb_step;
         sb = sb >= tcap ? sb - tcap : sb;
         block_barrier();
