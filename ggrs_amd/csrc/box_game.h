@@ -324,21 +324,32 @@ __device__ inline void advance_player_rec(float& x, float& y, float& vx, float& 
 // after the multiplication (RN(k * -v) == -RN(k * v) exactly): (d & keep) ^ (sgn ^ (q & keep)).
 // KATs against the oracle: test_gpu_step_forms.py::test_step_form[rec_q-*], and test_chain with the
 // next step's raw sin/cos computed in the hook.
-// One text for both forms below: kTurn false leaves out the turn and the hook (rot is not read).
-template <bool kTurn, typename Hook>
-__device__ __forceinline__ void advance_player_rec_q_body(float& x, float& y, float& vx, float& vy, float& rot,
-                                                          const InputRec& in, float sr, float cr, uint32_t qs,
-                                                          uint32_t qc, Hook&& hook) {
-  ggrs_f2 vel = ggrs_f2{vx, vy} * kFriction;
+// One text for every form below, in two pieces.  The increment reads the sin/cos and the record's
+// (sgn, keep) only, the rest of the step reads the increment and, for its turn, the record's
+// (delta, thr): a caller that knows a step's sin/cos and record ahead of the step (the split
+// SyncTest kernel's block pass, synctest_sincos_block.h) computes the increment there and runs
+// advance_player_inc_body on it.
+struct VelInc {
+  uint32_t ix, iy;  // the f32 bits of the velocity increment
+};
+__device__ __forceinline__ VelInc rec_q_increment(float sr, float cr, uint32_t qs, uint32_t qc, uint32_t sgn,
+                                                  uint32_t keep) {
   const ggrs_f2 d = ggrs_f2{cr, sr} * kMovementSpeed;
   const float dx = d.x, dy = d.y;
-  const uint32_t wx = in.sgn ^ (qc & in.keep), wy = in.sgn ^ (qs & in.keep);
-  const uint32_t ix = (__builtin_bit_cast(uint32_t, dx) & in.keep) ^ wx;
-  const uint32_t iy = (__builtin_bit_cast(uint32_t, dy) & in.keep) ^ wy;
-  vel = vel + ggrs_f2{__builtin_bit_cast(float, ix), __builtin_bit_cast(float, iy)};
+  const uint32_t wx = sgn ^ (qc & keep), wy = sgn ^ (qs & keep);
+  const uint32_t ix = (__builtin_bit_cast(uint32_t, dx) & keep) ^ wx;
+  const uint32_t iy = (__builtin_bit_cast(uint32_t, dy) & keep) ^ wy;
+  return VelInc{ix, iy};
+}
+// kTurn false leaves out the turn and the hook (rot, delta and thr are not read).
+template <bool kTurn, typename Hook>
+__device__ __forceinline__ void advance_player_inc_body(float& x, float& y, float& vx, float& vy, float& rot,
+                                                        const VelInc inc, uint32_t delta, uint32_t thr, Hook&& hook) {
+  ggrs_f2 vel = ggrs_f2{vx, vy} * kFriction;
+  vel = vel + ggrs_f2{__builtin_bit_cast(float, inc.ix), __builtin_bit_cast(float, inc.iy)};
   if constexpr (kTurn) {
-    const float a = rot + __builtin_bit_cast(float, in.delta);
-    rot = a + (a < 0.0f ? kTwoPi : (a >= __builtin_bit_cast(float, in.thr) ? -kTwoPi : 0.0f));
+    const float a = rot + __builtin_bit_cast(float, delta);
+    rot = a + (a < 0.0f ? kTwoPi : (a >= __builtin_bit_cast(float, thr) ? -kTwoPi : 0.0f));
     hook(rot);
   }
   const ggrs_f2 sq = vel * vel;
@@ -358,6 +369,13 @@ __device__ __forceinline__ void advance_player_rec_q_body(float& x, float& y, fl
   vx = vel.x;
   vy = vel.y;
 }
+template <bool kTurn, typename Hook>
+__device__ __forceinline__ void advance_player_rec_q_body(float& x, float& y, float& vx, float& vy, float& rot,
+                                                          const InputRec& in, float sr, float cr, uint32_t qs,
+                                                          uint32_t qc, Hook&& hook) {
+  const VelInc inc = rec_q_increment(sr, cr, qs, qc, in.sgn, in.keep);
+  advance_player_inc_body<kTurn>(x, y, vx, vy, rot, inc, in.delta, in.thr, hook);
+}
 template <typename Hook = NoHook>
 __device__ inline void advance_player_rec_q(float& x, float& y, float& vx, float& vy, float& rot, const InputRec& in,
                                             float sr, float cr, uint32_t qs, uint32_t qc, Hook&& hook = Hook()) {
@@ -371,6 +389,16 @@ __device__ inline void advance_player_rec_q_turned(float& x, float& y, float& vx
                                                    float sr, float cr, uint32_t qs, uint32_t qc) {
   float rot = 0.0f;
   advance_player_rec_q_body<false>(x, y, vx, vy, rot, in, sr, cr, qs, qc, NoHook());
+}
+// The same step from an increment computed ahead of it (rec_q_increment of the step's sin/cos and
+// record): without the turn, and with the turn of the record's (delta, thr).
+__device__ inline void advance_player_inc_turned(float& x, float& y, float& vx, float& vy, const VelInc inc) {
+  float rot = 0.0f;
+  advance_player_inc_body<false>(x, y, vx, vy, rot, inc, 0u, 0u, NoHook());
+}
+__device__ inline void advance_player_inc(float& x, float& y, float& vx, float& vy, float& rot, const VelInc inc,
+                                          uint32_t delta, uint32_t thr) {
+  advance_player_inc_body<true>(x, y, vx, vy, rot, inc, delta, thr, NoHook());
 }
 
 __device__ inline void advance_player_lean(float& x, float& y, float& vx, float& vy, float& rot,

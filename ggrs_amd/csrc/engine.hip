@@ -612,10 +612,13 @@ __global__ __launch_bounds__(kWave) void synctest_pipelined_v4_kernel(PipeParams
 // advance, the eight turns of a block and their sin/cos are taken out of the steps: rot evolves
 // from rot and the step's InputRec alone, all eight records are in registers at the block's head,
 // so every lane runs the block's eight turns there and the lane of role j evaluates the sin/cos of
-// the rot after step j, once, into a 16-byte LDS entry that step j + 1 reads on every lane
-// (synctest_sincos_block.h: one f64 polynomial pass per block instead of eight); wave 1 (the
-// consumer) takes part in the core blocks only and does their saves and their batch (whose sin/cos
-// is the lane's own entry of the block), one block behind the producer.
+// the rot after step j, once, folds it with its own record of step j + 1's row into that step's
+// velocity increment, and publishes the increment as an 8-byte LDS entry that step j + 1 reads on
+// every lane (synctest_sincos_block.h: one f64 polynomial pass and one increment per lane and block
+// instead of eight; a core step is friction, the entry, the clamp test, the position, the hand-off
+// and the role rotation); wave 1 (the consumer) takes part in the core blocks only and does their
+// saves and their batch (whose increment is the lane's own entry of the block), one block behind
+// the producer.
 // In a core step every role holds the post-advance state of the same frame,
 // so the consumer saves once per step, not once per role (synctest_save.h): it compares the roles'
 // states bit for bit, then lane (session, role j, player) checksums and stores step j's cell --
@@ -666,16 +669,17 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   __shared__ __attribute__((aligned(16))) uint8_t lds_stash[2 * kB * kSlot];  // slots, then the dump
   // Split kernel: the producer wave's hand-off to the consumer wave, two buffers of one 8-step
   // block each.  A step's slot holds every lane's post-advance state (fields 0..3 as one uint4 per
-  // lane, then field 4 as one word per lane); lds_hrec holds, per buffer and lane, the InputRec
-  // the lane's batch sub-step needs (lds_raw is re-read while the consumer still works).
+  // lane, then field 4 as one word per lane); lds_hrec holds, per buffer and lane, the (delta, thr)
+  // of the InputRec the lane's batch sub-step takes (lds_raw is re-read while the consumer still
+  // works; the record's other half is already in the lane's increment entry).
   constexpr int kHSlot = kSaveHandSlot;
   static_assert(!kSplit || (P == kSavePlayers && CD == kSaveCd && kB == kSaveCd), "synctest_save.h is the split kernel's block");
   __shared__ __attribute__((aligned(16))) uint8_t lds_hand[kSplit ? 2 * kB * kHSlot : 16];
-  __shared__ uint4 lds_hrec[kSplit ? 2 * kWave : 1];
-  // Split kernel: the sin/cos entries of a core block (synctest_sincos_block.h), one per lane,
+  __shared__ uint2 lds_hrec[kSplit ? 2 * kWave : 1];
+  // Split kernel: the increment entries of a core block (synctest_sincos_block.h), one per lane,
   // double-buffered with the hand-off: the producer writes block k's at the head of block k and
   // reads them in its steps, the consumer reads its own lane's for block k's batch.
-  __shared__ __attribute__((aligned(16))) uint8_t lds_sc[kSplit ? 2 * kSincosBlockBytes : 16];
+  __shared__ __attribute__((aligned(16))) uint8_t lds_sc[kSplit ? 2 * kIncBlockBytes : 16];
   __shared__ int32_t lds_ctl[2];  // split kernel: the number of core blocks and their first step
   const int wl = threadIdx.x & (kWave - 1);
   // wave 0 produces, wave 1 consumes (one-wave kernel: the only wave does both).  Measured
@@ -887,6 +891,8 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   auto on_hold_grid = [&](int32_t t) { return ((t - p.f0) & (kHold - 1)) == 0; };
   // the InputRec of a raw input byte
   auto tab_rec = [&](uint32_t raw) -> uint4 { return lds_tab[raw & kInputRecMask]; };
+  // its (delta, thr) alone: all a core step of the split kernel's block takes from its record
+  auto tab_turn = [&](uint32_t raw) -> uint2 { return *reinterpret_cast<const uint2*>(&lds_tab[raw & kInputRecMask]); };
 
   uint32_t acc = 0;
   const uint32_t in_at = (uint32_t)in_lane;
@@ -1001,16 +1007,17 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
       w[q] = Pp == 2 ? (uint32_t)__builtin_amdgcn_update_dpp((int)w[q], (int)w[q], 0x112, 0xF, 0xF, false) : nx[q];
   };
 
-  // The split kernel's core step (the producer's half): position and velocity from the sin/cos of
-  // the rot the step starts from, the hand-off of fields 0..3 (every lane's post-advance state goes
-  // to the consumer, which compares, checksums and stores it and runs the block's batch from the
-  // role cd-1 entries) and their role rotation.  rot is not here: the block's turns, their sin/cos
-  // and the hand-off's field 4 are the block's pass (synctest_sincos_block.h), and w[4] is the
-  // lane's own rot at the block's head.
-  auto split_core_step = [&](const uint4 in, uint32_t slot_off) {
+  // The split kernel's core step (the producer's half): position and velocity from the step's
+  // velocity increment (the block's entry, or the one carried over), the hand-off of fields 0..3
+  // (every lane's post-advance state goes to the consumer, which compares, checksums and stores it
+  // and runs the block's batch from the role cd-1 entries) and their role rotation.  rot is not
+  // here: the block's turns, their sin/cos, the increments and the hand-off's field 4 are the
+  // block's pass (synctest_sincos_block.h), and w[4] is the lane's own rot at the block's head.
+  // No record reaches the step.
+  auto split_core_step = [&](const VelInc inc, uint32_t slot_off) {
     float x = __builtin_bit_cast(float, w[0]), y = __builtin_bit_cast(float, w[1]);
     float vx = __builtin_bit_cast(float, w[2]), vy = __builtin_bit_cast(float, w[3]);
-    advance_player_rec_q_turned(x, y, vx, vy, rec_of(in), sc_s, sc_c, sc_qs, sc_qc);
+    advance_player_inc_turned(x, y, vx, vy, inc);
     w[0] = __builtin_bit_cast(uint32_t, x);
     w[1] = __builtin_bit_cast(uint32_t, y);
     w[2] = __builtin_bit_cast(uint32_t, vx);
@@ -1024,8 +1031,9 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
   // 8): role j < count advances step tb + j's stash -- chain cb = tb + j - (cd - 1), its frame cb,
   // with input cb, which step tb + j + 1 reads -- and stores the display checksum of frame cb + 1.
   // batch_run: the sub-step itself, from the stashed state v and the input `in` (core: the
-  // InputRec, else the raw byte); batch: the one-wave form, which reads both from this wave's LDS.
-  uint4 batch_sc = make_uint4(0u, 0u, 0u, 0u);  // split kernel's consumer: the lane's sin/cos entry of the block
+  // InputRec -- the split kernel's consumer: its (delta, thr) -- else the raw byte); batch: the
+  // one-wave form, which reads both from this wave's LDS.
+  VelInc batch_inc{0u, 0u};  // split kernel's consumer: the lane's increment entry of the block
   auto batch_run = [&](auto core_tag, int32_t tb, int count, uint32_t(&v)[5], auto in) {
     constexpr bool kCore = decltype(core_tag)::value;
     constexpr bool kEdge = IsEdge<decltype(core_tag)>::value;
@@ -1036,17 +1044,17 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
       float vx = __builtin_bit_cast(float, v[2]), vy = __builtin_bit_cast(float, v[3]);
       float rot = __builtin_bit_cast(float, v[4]);
       if constexpr (kCore) {
-        float bs, bc;
-        uint32_t bqs, bqc;
         if constexpr (kSplit && !kEdge) {
-          // the consumer's batch: rot is the rot of hand-off slot j, r[j] of the block, whose
-          // sin/cos this lane's own entry holds (synctest_sincos_block.h)
-          bs = __builtin_bit_cast(float, batch_sc.x), bc = __builtin_bit_cast(float, batch_sc.y);
-          bqs = batch_sc.z, bqc = batch_sc.w;
+          // the consumer's batch: rot is the rot of hand-off slot j, r[j] of the block; this lane's
+          // own entry is the increment from its sin/cos and this sub-step's record
+          // (synctest_sincos_block.h), so only the turn is left to take from the record
+          advance_player_inc(x, y, vx, vy, rot, batch_inc, in.x, in.y);
         } else {
+          float bs, bc;
+          uint32_t bqs, bqc;
           glibc_sincosf_domain_raw(rot, &bs, &bc, &bqs, &bqc);
+          advance_player_rec_q(x, y, vx, vy, rot, rec_of(in), bs, bc, bqs, bqc);
         }
-        advance_player_rec_q(x, y, vx, vy, rot, rec_of(in), bs, bc, bqs, bqc);
       } else {
         advance_player(x, y, vx, vy, rot, (uint32_t)in);
       }
@@ -1125,8 +1133,8 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
           bv[0] = a.x, bv[1] = a.y, bv[2] = a.z, bv[3] = a.w;
           bv[4] = *reinterpret_cast<const uint32_t*>(st + kWave * 16 + hand_first * 4);
         }
-        const uint4 brec = lds_hrec[(k & 1) * kWave + wl];
-        batch_sc = *reinterpret_cast<const uint4*>(lds_sc + (k & 1) * kSincosBlockBytes + wl * kSincosEntry);
+        const uint2 brec = lds_hrec[(k & 1) * kWave + wl];
+        batch_inc = increment_block_entry(lds_sc + (k & 1) * kIncBlockBytes, wl, j, j);
         bad |= synctest_save_block(hb, save, rs_ring, R, (uint32_t)sr, t, wl, j, save_lanes);
         sr = sr + kB >= R ? sr + kB - R : sr + kB;  // R > 8
         batch_run(std::true_type(), t, kB, bv, brec);
@@ -1176,17 +1184,31 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
     for (int u = 0; u < kB; u++) b[u] = lds_raw[ip + u * ROW];
     if constexpr (kSplit) b[kB] = lds_raw[ip + (uint32_t)((j & (kB - 1)) + 1) * ROW];
   };
-  auto block_recs = [&](const uint32_t(&b)[kRecs], uint4(&rec)[kRecs]) {
+  // What the loop holds of the next core block's records.  One-wave kernel: all eight, whole.
+  // Split kernel: of the eight their (delta, thr), which is all the block's chain reads of them,
+  // and the lane's own next-step record (row t + (j & 7) + 1), whole.
+  uint4 ahead[kB];
+  uint2 turns[kB];
+  uint4 own = make_uint4(0u, 0u, 0u, 0u);
+  auto block_recs = [&](const uint32_t(&b)[kRecs]) {
 #pragma unroll
-    for (int u = 0; u < kRecs; u++) rec[u] = tab_rec(b[u]);
+    for (int u = 0; u < kB; u++) {
+      if constexpr (kSplit) {
+        turns[u] = tab_turn(b[u]);
+      } else {
+        ahead[u] = tab_rec(b[u]);
+      }
+    }
+    if constexpr (kSplit) own = tab_rec(b[kB]);
   };
-  uint4 ahead[kRecs];  // the next core block's records
+  uint4 rec0 = make_uint4(0u, 0u, 0u, 0u);  // split kernel: the first core block's step-0 record, whole
   if (n_core > 0) {
     // the first core block's: issued before publish(), whose barrier waits for them anyway
     if (on_hold_grid(t)) hold_rows(t);
     uint32_t b[kRecs];
     block_raw(t, b);
-    block_recs(b, ahead);
+    block_recs(b);
+    if constexpr (kSplit) rec0 = tab_rec(b[0]);
   }
   if constexpr (kSplit) {
     // The steps so far have stored ring and trace cells that the consumer's steps store again
@@ -1200,10 +1222,15 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
     pend_ck = pend_first = 0;
     pend_lanes = cmp_lanes;
     glibc_sincosf_domain_raw(__builtin_bit_cast(float, w[4]), &sc_s, &sc_c, &sc_qs, &sc_qc);
+    // split kernel: the increment the next core step 0 runs on -- the first block's from the
+    // evaluation above and its step-0 record, every later block's the previous block's entry of
+    // role 7 (whose own record is row t + 8's)
+    VelInc inc_next{0u, 0u};
+    if constexpr (kSplit) inc_next = rec_q_increment(sc_s, sc_c, sc_qs, sc_qc, rec0.z, rec0.w);
     // the producer is one dependent chain: it issues first when both waves of a SIMD are ready,
-    // the consumer fills the cycles it leaves (measured, DESIGN.md §5: 0.154 -> 0.146 ms with the
-    // per-role saves; with one save per step, where the consumer is the shorter wave, 0.131 ->
-    // 0.115 ms)
+    // the consumer fills the cycles it leaves (measured on earlier forms of the block, DESIGN.md
+    // §5: 0.154 -> 0.146 ms with the per-role saves; with one save per step, where the consumer is
+    // the shorter wave, 0.131 -> 0.115 ms)
     if constexpr (kSplit) __builtin_amdgcn_s_setprio(1);
     for (int32_t k = 0; k < n_core; ++k, t += kB) {
       // Block k's records were read during block k - 1, ahead of its barrier (whose lgkmcnt(0)
@@ -1212,68 +1239,62 @@ __global__ __launch_bounds__(kSplit ? 2 * kWave : kWave) void synctest_pipelined
       if (k > 0 && on_hold_grid(t) && hold_rows(t)) {
         uint32_t b[kRecs];
         block_raw(t, b);
-        block_recs(b, ahead);
+        block_recs(b);
       }
-      // Block k + 1's raw bytes now; the record of its step u once step u here has used the
-      // register (no second set, no copies) -- but step 7's and the batch's after step kAheadAt
-      // into registers of their own, so that the barrier waits for no read issued just before it.
-      // (Past the last core block these are the edge steps' rows, or the slack row, and unused.)
+      // Block k + 1's raw bytes now.  (Past the last core block these are the edge steps' rows, or
+      // the slack row, and unused.)
       uint32_t b[kRecs];
       block_raw(t + kB, b);
-      uint4 last = ahead[kB - 1];
-      // Split kernel: block k goes into hand-off buffer k & 1, which the consumer read for block
-      // k - 2 before it arrived at the barrier this wave passed last; the barrier below hands
-      // block k over.
-      const uint32_t slot0 = kSplit ? (uint32_t)(k & 1) * (kB * kHSlot) : 0u;
-      if constexpr (kSplit) lds_hrec[(k & 1) * kWave + wl] = ahead[kB];
-      // Split kernel: the block's eight turns and its one sin/cos pass (synctest_sincos_block.h),
-      // from this lane's own rot and the block's records.  Step 0 runs on the sin/cos carried in
-      // registers (the previous block's entry of role 7, before the first block the evaluation
-      // above), step u > 0 on the entry of role u - 1, read one step ahead.
-      const uint8_t* scb = lds_sc + (kSplit ? (k & 1) * kSincosBlockBytes : 0);
-      uint4 sc_next = make_uint4(0u, 0u, 0u, 0u);
       if constexpr (kSplit) {
-        const InputRec recs[kB] = {rec_of(ahead[0]), rec_of(ahead[1]), rec_of(ahead[2]), rec_of(ahead[3]),
-                                   rec_of(ahead[4]), rec_of(ahead[5]), rec_of(ahead[6]), rec_of(ahead[7])};
-        float rr[kB];
-        block_rot_chain(__builtin_bit_cast(float, w[4]), recs, rr);
-        sincos_block_pass(lds_hand + slot0, lds_sc + (k & 1) * kSincosBlockBytes, wl, j, rr);
-        w[4] = __builtin_bit_cast(uint32_t, rr[kB - 1]);
-      }
+        // Block k goes into hand-off buffer k & 1, which the consumer read for block k - 2 before
+        // it arrived at the barrier this wave passed last; the barrier below hands block k over.
+        const uint32_t slot0 = (uint32_t)(k & 1) * (kB * kHSlot);
+        uint8_t* scb = lds_sc + (k & 1) * kIncBlockBytes;
+        lds_hrec[(k & 1) * kWave + wl] = make_uint2(own.x, own.y);
+        // The block's eight turns and its one pass (synctest_sincos_block.h), from this lane's own
+        // rot and the block's records: the turns read (delta, thr) of all eight, the pass (sgn,
+        // keep) of the lane's own next-step record, and that is all a block reads of its records.
+        {
+          float rr[kB];
+          block_rot_chain(__builtin_bit_cast(float, w[4]), turns, rr);
+          increment_block_pass(lds_hand + slot0, scb, wl, j, rr, own.z, own.w);
+          w[4] = __builtin_bit_cast(uint32_t, rr[kB - 1]);
+        }
+        wave_lds_sync();  // the entries are written
+        // Step 0 runs on the increment carried in registers, step u > 0 on the entry of role
+        // u - 1, read one step ahead.  Block k + 1's records after step kAheadAt, all at once (this
+        // block's are used up), so that the barrier waits for no read issued just before it.
 #pragma unroll
-      for (int u = 0; u < kB; u++) {
-        if constexpr (kSplit) {
-          if (u > 0) {
-            sc_s = __builtin_bit_cast(float, sc_next.x), sc_c = __builtin_bit_cast(float, sc_next.y);
-            sc_qs = sc_next.z, sc_qc = sc_next.w;
-          }
-          if (u == 0) wave_lds_sync();  // the entries are written
-          sc_next = sincos_block_entry(scb, wl, j, u);
-          split_core_step(ahead[u], slot0 + (uint32_t)(u * kHSlot));
-        } else {
-          step(std::true_type(), t + u, ahead[u], slot0 + (uint32_t)(u * kSlot));
+        for (int u = 0; u < kB; u++) {
+          const VelInc inc = inc_next;
+          inc_next = increment_block_entry(scb, wl, j, u);
+          split_core_step(inc, slot0 + (uint32_t)(u * kHSlot));
+          if (u == kAheadAt) block_recs(b);
         }
-        if (u < kB - 1) ahead[u] = tab_rec(b[u]);
-        if (u == kAheadAt) {
-          last = tab_rec(b[kB - 1]);
-          if constexpr (kSplit) ahead[kB] = tab_rec(b[kB]);
-        }
-      }
-      ahead[kB - 1] = last;
-      if constexpr (kSplit) {
-        // role 7's entry: the next block's step 0 (after the last core block, the edge block's)
-        sc_s = __builtin_bit_cast(float, sc_next.x), sc_c = __builtin_bit_cast(float, sc_next.y);
-        sc_qs = sc_next.z, sc_qc = sc_next.w;
         sb = sb + sb_step;
         sb = sb >= tcap ? sb - tcap : sb;
         block_barrier();
       } else {
+        // The record of block k + 1's step u once step u here has used the register (no second
+        // set, no copies) -- but step 7's after step kAheadAt into registers of its own, so that
+        // no read is issued just before the batch.
+        uint4 last = ahead[kB - 1];
+#pragma unroll
+        for (int u = 0; u < kB; u++) {
+          step(std::true_type(), t + u, ahead[u], (uint32_t)(u * kSlot));
+          if (u < kB - 1) ahead[u] = tab_rec(b[u]);
+          if (u == kAheadAt) last = tab_rec(b[kB - 1]);
+        }
+        ahead[kB - 1] = last;
         batch(std::true_type(), t, kB);
       }
     }
     if constexpr (kSplit) {
       __builtin_amdgcn_s_setprio(0);
       sr = (sr + n_core * kB) % R;
+      // the edge block behind the core blocks runs on raw sin/cos again: of the lane's own rot,
+      // once per launch
+      if (edge_ok) glibc_sincosf_domain_raw(__builtin_bit_cast(float, w[4]), &sc_s, &sc_c, &sc_qs, &sc_qc);
       // the consumer's last store has reached memory (it drains them before this barrier)
       block_barrier();
     } else {
