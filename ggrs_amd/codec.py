@@ -115,8 +115,9 @@ def set_direct(on):
 
 
 def set_kernels(form):
-    """Kernel form for later calls: "default" (lane-cooperative where W*B <= 64, else LDS-staged),
-    "direct" or "staged" (thread-per-packet forms)."""
+    """Kernel form for later calls, all one thread per packet: "default" (the run-level form where
+    input_bytes is 1, 2 or 4 and W*B <= 64 whole dwords, else LDS-staged), "staged" or "direct" (a
+    form whose LDS does not fit falls to the next one)."""
     L = _lib.lib()
     _bind(L)
     _lib.check(L.ggrs_codec_set_direct(KERNEL_FORMS[form]))

@@ -13,7 +13,11 @@ receiver's 2 max_prediction retention; at most max_packet_inputs frames.  The pa
 against the true remote bytes of frame start - 1 (zeros before frame 0).  Damage per (call,
 session): "truncate", "random" (random bytes), "withhold", "duplicate" (the previous packet once
 more), "old_reference" (a start whose reference the receiver no longer keeps), "gap" (a start past
-last_recv + 1), "ahead" (frames beyond the call) and "overlong" (max_packet_inputs + 1 frames).
+last_recv + 1), "ahead" (frames beyond the call) and "overlong" (max_packet_inputs + 1 frames); and the
+kinds of tests/codec_cases.py's recode (RECODE): the same inputs in other bytes -- runs split, zero-length
+runs, padded varints, input_sizes = Some(zero deltas), bytes after the stream -- which deliver as the
+packet would have, and Some(..) with uneven or negative sizes over the same stream, which are dropped
+with UNSUPPORTED / E_DELTA.  A recoded packet that outgrows the stride goes out as it was.
 
 A receiver: UdpProtocol::on_input (:564-642) as include/ggrs_amd.h restates it --
   1. gap: last_recv != NULL and last_recv + 1 < start (the assert!, :588-590), or a first packet with
@@ -32,12 +36,14 @@ import ctypes
 import numpy as np
 
 from oracle import oracle as O
+from tests import codec_cases as C
 
 NULL_FRAME = -1
 E_INVALID, E_PRECONDITION = -1, -2
 CODEC_E_CAP, CODEC_E_INVALID, CODEC_UNSUPPORTED = -4, -5, -6
 NO_REFERENCE, STOPPED = -16, -17
 DAMAGE = ("truncate", "random", "withhold", "duplicate", "old_reference", "gap")
+RECODE = C.ACCEPTING + C.REJECTING  # applied only where a caller's damage dict names them
 
 
 def max_packet_bytes(B, W):
@@ -193,6 +199,8 @@ def run(rows, arrive, local_mask, max_prediction, max_packet_inputs=64, stride=N
                         kind = None
                     else:
                         start, data = prev_packet
+                elif kind in RECODE:
+                    data, kind = recoded(data, kind, B, stride, (seed, c, s))
                 if kind:
                     out["applied"][(c, s)] = kind
                 if kind not in ("duplicate", "withhold"):
@@ -206,6 +214,36 @@ def run(rows, arrive, local_mask, max_prediction, max_packet_inputs=64, stride=N
         if recv.stop_call is not None:
             out["stop_call"][s], out["error"][s] = recv.stop_call, recv.error
     return out
+
+
+def recoded(data, kind, B, stride, key):
+    """codec_cases.recode with a generator of its own (the sender's random overlaps stay what they are
+    without it): -> (bytes, kind), or (data, None) where the kind has no other form of this packet
+    within the stride."""
+    new = C.recode(data, kind, np.random.default_rng(list(key)), B)
+    return (data, None) if new is None or new == data or len(new) > stride else (new, kind)
+
+
+def recode_list(arrive, seed, every=3, per_session=5):
+    """One kind of RECODE per `every`-th session, the kinds in turn, at `per_session` of the calls where
+    the session's schedule rises (where the sender sends)."""
+    calls, S = arrive.shape
+    rng = np.random.default_rng(seed)
+    damage = {}
+    for i, s in enumerate(range(0, S, every)):
+        rises = np.nonzero(arrive[1:, s] > arrive[:-1, s])[0] + 1
+        for c in rng.choice(rises, min(per_session, len(rises)), replace=False):
+            damage[(int(c), s)] = RECODE[i % len(RECODE)]
+    return damage
+
+
+def recode_case(P, local_mask, S=66, calls=160, max_prediction=8, seed=3):
+    """The recode tests' inputs (tests/test_packet_feed_model.py on the CPU, tests/test_gpu_p2p_packets.py
+    on the device): rows, a schedule per session (stalls with bursts, jitter), the recode list."""
+    rows = np.stack([O.gen_inputs(O.session_seed(s, 0x4EC0 + P), calls, P, 1) for s in range(S)], axis=1)
+    arrive = np.stack([O.stall_schedule(calls, max_prediction, seed * 1000 + s, stall_every=40 if s % 2 else 10 ** 9)
+                       for s in range(S)], axis=1).astype(np.int32)
+    return rows, arrive, recode_list(arrive, seed)
 
 
 def damage_list(arrive, max_prediction, seed, every=7):

@@ -15,7 +15,8 @@ max_packet_inputs frames, encoded against the host's frame start - 1 (zeros befo
 input is all players' bytes in player order.  Damage per (call, session): "truncate", "random"
 (random bytes), "withhold", "duplicate" (the previous packet once more), "old_reference" (a start
 whose reference the receiver no longer keeps), "gap" (a start past last_recv + 1) and "overlong"
-(max_packet_inputs + 1 frames).
+(max_packet_inputs + 1 frames); and packet_feed_model.RECODE's kinds (tests/codec_cases.py's recode: the
+same inputs in other bytes, or Some(..) sizes the feed refuses), applied as packet_feed_model.run does.
 
 A receiver: UdpProtocol::on_input (:564-642) as include/ggrs_amd.h restates it for the spectators --
   1. gap: last_recv != NULL and last_recv + 1 < start (the assert!, :588-590), or a first packet with
@@ -150,6 +151,8 @@ def run_feed(rows, host_upto, max_prediction=8, max_packet_inputs=64, stride=Non
                         kind = None
                     else:
                         start, data = prev_packet
+                elif kind in PF.RECODE:
+                    data, kind = PF.recoded(data, kind, P, stride, (seed, c, s))
                 if kind:
                     out["applied"][(c, s)] = kind
                 if kind not in ("duplicate", "withhold"):
@@ -277,6 +280,7 @@ def clock_case(S=130, calls=200):
 
 
 DAMAGED = dict(P=2, cap=256, W=24, mp=8, mfb=10, speed=3)
+RECODED = dict(P=2, cap=512, W=24, mp=8, mfb=10, speed=3)
 
 
 @functools.lru_cache(maxsize=None)
@@ -288,3 +292,17 @@ def damage_case(S=130, calls=200, seed=5):
                           for s in range(S)], axis=1).astype(np.int32)
     damage = damage_list(host_upto, k["mp"], seed)
     return rows, host_upto, damage, run_feed(rows, host_upto, k["mp"], k["W"], seed=9, damage=damage)
+
+
+@functools.lru_cache(maxsize=None)
+def recode_case(S=66, calls=160, seed=4):
+    """One of packet_feed_model.RECODE's kinds in every 3rd session, at several of its calls; the hosts
+    stay within one window, so a table-fed engine can hold the same rows.
+    -> (rows, host_upto, damage, feed, the feed of the same packets as the sender encoded them)"""
+    k = RECODED
+    rows = host_inputs(S, calls + 64, k["P"], 0x4EC0)
+    host_upto = np.stack([O.stall_schedule(calls, k["mp"], seed * 1000 + s, stall_every=40 if s % 2 else 10 ** 9)
+                          for s in range(S)], axis=1).astype(np.int32)
+    damage = PF.recode_list(host_upto, seed)
+    return (rows, host_upto, damage, run_feed(rows, host_upto, k["mp"], k["W"], seed=21, damage=damage),
+            run_feed(rows, host_upto, k["mp"], k["W"], seed=21))

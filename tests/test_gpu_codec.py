@@ -30,16 +30,16 @@ def gpu(a):
 
 @pytest.fixture(params=["default", "staged", "direct"])
 def kernels(request):
-    """Every kernel form: default (lane-cooperative where W*B <= 64 and rows are whole dwords),
-    thread-per-packet LDS-staged, and direct."""
+    """Every kernel form, all thread-per-packet: default (run-level where input_bytes is 1, 2 or 4,
+    W*B <= 64 and rows are whole dwords, else LDS-staged), LDS-staged, and direct."""
     from ggrs_amd import codec
     codec.set_kernels(request.param)
     yield request.param
     codec.set_kernels("default")
 
 
-# W*B: 8, 32 (lane-cooperative segments of 8 / 32 lanes), 132, 128 (thread-per-packet staged), 7
-# (direct); then 16 (the bench shape), 64, 4, 12 (segments of 16 / 64 / 4 / 16 lanes)
+# W*B: 8, 32 (run-level, 2 / 8 dwords of delta stream), 132, 128 (over the staged form's LDS: direct), 7
+# (direct); then 16 (the bench shape), 64, 4, 12 (run-level, 4 / 16 / 1 / 4 dwords; 64 encodes staged)
 @pytest.mark.parametrize("N,W,B,held", [(5000, 8, 1, True), (3000, 16, 2, False), (2000, 33, 4, False),
                                          (1000, 128, 1, True), (257, 1, 7, False), (4000, 8, 2, True),
                                          (3000, 16, 4, True), (2000, 4, 1, False), (2000, 12, 1, True),

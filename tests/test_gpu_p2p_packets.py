@@ -197,6 +197,42 @@ def test_damaged_packets(oracle):
     assert (errors[undamaged] == 0).all()
 
 
+@pytest.mark.parametrize("P,local", [(2, (0,)), (3, (0,))])
+def test_recoded_packets(oracle, P, local):
+    """Every third session gets, at several of its calls, the sender's packet in other bytes
+    (tests/codec_cases.py's recode; 1 and 2 input bytes): runs split, zero-length runs, padded varints,
+    input_sizes = Some(zero deltas) and bytes after the stream deliver as the packet would have (status
+    1); Some(..) with uneven or negative sizes is dropped with UNSUPPORTED / E_DELTA.  Status and ack of
+    every (call, session) equal the model's, A equals the schedule-fed B, the running sessions the
+    oracle's."""
+    import collections
+    from tests import codec_cases as C
+    mask, mp = sum(1 << k for k in local), 8
+    rows, arrive, damage = M.recode_case(P, mask, max_prediction=mp)
+    calls, S = arrive.shape
+    m = M.run(rows, arrive, mask, mp, seed=9, damage=damage)
+    plain = M.run(rows, arrive, mask, mp, seed=9)
+    times = collections.Counter(m["applied"].values())
+    assert set(times) == set(M.RECODE) and min(times.values()) >= 5, times
+    assert (m["stop_call"] == -1).all()
+    A, B = engines(S, P, local, mp, calls)
+    events = np.zeros((calls, S), np.uint8)
+    assert run_pair(A, B, rows, m, None, (1, 3, 60, 17, calls - 81), mask) == calls
+    status, ack = A.packet_results(0, calls)
+    assert (status == m["status"]).all(), np.argwhere(status != m["status"])[:5]
+    assert (ack == m["ack"]).all()
+    for (c, s), kind in m["applied"].items():
+        want = 1 if kind in C.ACCEPTING else C.RECODE_STATUS[kind]
+        assert status[c, s] == want, (c, s, kind, status[c, s])
+    accepting = sorted({s for (_, s), kind in m["applied"].items() if kind in C.ACCEPTING})
+    assert ((status == 1) == (plain["status"] == 1))[:, accepting].all() and (ack == arrive)[:, accepting].all()
+    assert_same(A, B)
+    frames, skipped, errors = A.sessions()
+    assert (errors == 0).all()
+    recoded = sorted({s for _, s in m["applied"]})
+    check_sessions(A, m["rows"], m["arrive"], events, recoded + [s for s in range(1, S, 6)], calls)
+
+
 def test_long_bursts_and_overlong_packets(oracle):
     """A stall of 40 calls, then one packet of 40+ frames (max_packet_inputs 64); every other
     session stalls for 66 calls and its sender's packet after the stall carries max_packet_inputs + 1

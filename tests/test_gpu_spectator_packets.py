@@ -182,6 +182,42 @@ def test_damaged_packets(oracle):
         assert (got["advanced"][feed["stop_call"][s]:, s] == 0).all()
 
 
+def test_recoded_packets(oracle):
+    """tests/codec_cases.py's recode on every third session, at several calls each: the accepting kinds
+    deliver (status 1 wherever the sender's own bytes would have), the rejecting ones are dropped with
+    UNSUPPORTED / E_DELTA; status, ack and every session equal the model's, and the table-fed engine
+    given the receivers' rows and words."""
+    import collections
+    from ggrs_amd import SpectatorEngine
+    from tests import codec_cases as C
+    rows, host_upto, damage, feed, plain = M.recode_case()
+    calls, S = host_upto.shape
+    k = M.RECODED
+    times = collections.Counter(feed["applied"].values())
+    assert set(times) == set(M.PF.RECODE) and min(times.values()) >= 5, times
+    assert (feed["stop_call"] == -1).all() and rows.shape[0] <= k["cap"]
+    ops = M.receive_then_advance(calls, 17)
+    A = feed_engine(S, k["P"], k["cap"], k["mfb"], k["speed"], k["W"], feed["stride"], calls, k["mp"])
+    got, model = assert_feed(A, feed, None, ops, k["cap"], k["mfb"], k["speed"], "recode")
+    status, _ = A.read_packet_results(0, calls)
+    for (c, s), kind in feed["applied"].items():
+        want = 1 if kind in C.ACCEPTING else C.RECODE_STATUS[kind]
+        assert status[c, s] == want, (c, s, kind, status[c, s])
+    accepting = sorted({s for (_, s), kind in feed["applied"].items() if kind in C.ACCEPTING})
+    assert (status[:, accepting] == plain["status"][:, accepting]).all()
+    assert (model["error"] == 0).all()
+    B = SpectatorEngine(S, num_players=k["P"], max_frames_behind=k["mfb"], catchup_speed=k["speed"],
+                        input_capacity=k["cap"], trace_capacity=calls)
+    B.add_inputs(0, feed["rows"])
+    B.add_arrivals(0, feed["recv"], None)
+    for op, n in ops:
+        if op == "adv":
+            B.advance_frames(n)
+    assert_equal(got, reads(B, calls), "table-fed engine")
+    A.close()
+    B.close()
+
+
 def test_both_feeds_agree_on_the_same_packets(oracle):
     """The damage case's packets go to a packet-fed SpectatorEngine and to a packet-fed P2PEngine whose
     two remote players are the spectator's two players: the receive side both kernels share

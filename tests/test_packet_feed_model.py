@@ -5,8 +5,12 @@ stays a schedule, and the oracle's P2PSession runs it; the ABI's three layers na
 import os
 import re
 
-import numpy as np
+import collections
 
+import numpy as np
+import pytest
+
+from tests import codec_cases as C
 from tests import packet_feed_model as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -80,6 +84,49 @@ def test_damaged_packets_leave_a_schedule_the_oracle_runs(oracle):
     assert 2 * ok >= len(damaged)
     # an undecodable or withheld packet costs frames only until the next one: the sender re-sends
     assert (m["ack"][-1, damaged] == arrive[-1, damaged])[m["stop_call"][damaged] < 0].all()
+
+
+@pytest.mark.parametrize("P,mask", [(2, 0b01), (3, 0b001)])
+def test_recoded_packets_deliver_or_are_dropped_by_their_kind(oracle, P, mask):
+    """The same inputs in other bytes (codec_cases.recode) on every third session, at several calls
+    each, with 1 and 2 input bytes: the accepting kinds change nothing but the packets, the rejecting
+    ones cost the packet (UNSUPPORTED / E_DELTA) and the sender's next one brings the frames."""
+    mp = 8
+    rows, arrive, damage = M.recode_case(P, mask, max_prediction=mp)
+    calls, S = arrive.shape
+    m = M.run(rows, arrive, mask, mp, seed=9, damage=damage)
+    plain = M.run(rows, arrive, mask, mp, seed=9)
+    times = collections.Counter(m["applied"].values())
+    assert set(times) == set(M.RECODE) and min(times.values()) >= 5, times
+    assert set(m["applied"]) <= set(damage) and (m["stop_call"] == -1).all()
+    assert (plain["arrive"] == arrive).all()
+    for (c, s), kind in m["applied"].items():
+        assert m["start"][c, s] >= 0  # (the bytes differ from the sender's own: recoded())
+        if kind in C.ACCEPTING:  # delivered wherever the undamaged packet would have been
+            assert m["status"][c, s] == plain["status"][c, s] == 1 and m["ack"][c, s] == arrive[c, s], (c, s, kind)
+        else:
+            assert m["status"][c, s] == C.RECODE_STATUS[kind] and m["ack"][c, s] == m["ack"][c - 1, s], (c, s, kind)
+    accepting = sorted({s for (_, s), kind in m["applied"].items() if kind in C.ACCEPTING})
+    rejecting = sorted({s for (_, s), kind in m["applied"].items() if kind in C.REJECTING})
+    untouched = sorted(set(range(S)) - set(rejecting))
+    for key in ("status", "ack", "arrive"):  # (not start: a dropped packet shifts the later random overlaps)
+        assert (m[key][:, untouched] == plain[key][:, untouched]).all(), key
+    assert (m["rows"] == rows).all()
+    assert ((m["status"] == 1) == (plain["status"] == 1))[:, accepting].all()
+    for s in rejecting + accepting[:4]:
+        eff = m["arrive"][:, s]
+        assert (np.diff(eff) >= 0).all() and (eff <= arrive[:, s]).all()
+        assert (s in accepting) or (eff < arrive[:, s]).any()
+        out = oracle.p2p_sched_run(m["rows"][:, s], eff, None, num_players=P, local_mask=mask, max_prediction=mp)
+        assert out["rc"] == 0, (s, out["rc"])
+
+
+def test_existing_damage_is_untouched_by_the_recode_kinds(oracle):
+    """The kinds apply only where a damage dict names them: the damage case's packets are what they were."""
+    assert M.DAMAGE == ("truncate", "random", "withhold", "duplicate", "old_reference", "gap")
+    assert not set(M.RECODE) & (set(M.DAMAGE) | {"ahead", "overlong"})
+    rows, arrive, damage = M.damage_case()
+    assert not set(damage.values()) & set(M.RECODE)
 
 
 def damage_kind(damage, s):

@@ -1,8 +1,11 @@
 """The spectator packet feed's Python model (tests/spectator_feed_model.py) against the model of the
 table-fed engine (tests/spectator_model.py) and the rules of include/ggrs_amd.h: what the device
 feed is compared with (tests/test_gpu_spectator_packets.py) must itself be right.  No GPU."""
+import collections
+
 import numpy as np
 
+from tests import codec_cases as C
 from tests import spectator_feed_model as M
 from tests import spectator_model as SM
 
@@ -83,6 +86,36 @@ def test_every_damage_kind_ends_as_the_rules_say(oracle):
             assert got["current_frame"][i] <= feed["ack"][stop, s]
         else:
             assert got["error"][i] == 0 and got["last_recv"][i] == host_upto[-1, s]
+
+
+def test_recoded_packets_deliver_or_are_dropped_by_their_kind(oracle):
+    """codec_cases.recode's kinds on every third session: the accepting ones leave every status, ack and
+    row as the sender's own bytes give them, the rejecting ones are dropped with their code and the
+    next packet re-sends the frames; the spectators over the feed run on."""
+    rows, host_upto, damage, feed, plain = M.recode_case()
+    calls, S = host_upto.shape
+    times = collections.Counter(feed["applied"].values())
+    assert set(times) == set(M.PF.RECODE) and min(times.values()) >= 5, times
+    assert (feed["stop_call"] == -1).all() and (plain["status"] >= 0).all()
+    for (c, s), kind in feed["applied"].items():
+        if kind in C.ACCEPTING:  # (the bytes differ from the sender's own: packet_feed_model.recoded)
+            assert feed["status"][c, s] == plain["status"][c, s] == 1 and feed["ack"][c, s] == plain["ack"][c, s]
+        else:
+            assert feed["status"][c, s] == C.RECODE_STATUS[kind] and feed["ack"][c, s] == feed["ack"][c - 1, s]
+    rejecting = sorted({s for (_, s), kind in feed["applied"].items() if kind in C.REJECTING})
+    others = sorted(set(range(S)) - set(rejecting))
+    for key in ("status", "ack", "recv", "rows"):  # (not start: a dropped packet shifts the later random overlaps)
+        assert (feed[key][:, others] == plain[key][:, others]).all(), key
+    assert (feed["ack"][-1] == host_upto[-1]).all()  # a dropped packet's frames come with the next one
+    recoded = sorted({s for _, s in feed["applied"]})
+    k = M.RECODED
+    ops = M.receive_then_advance(calls, 8)
+    got = M.run_spectators(subset_of(feed, None, recoded)[0], None, k["cap"], k["mfb"], k["speed"], ops=ops)
+    ref = M.run_spectators(subset_of(plain, None, recoded)[0], None, k["cap"], k["mfb"], k["speed"], ops=ops)
+    assert (got["error"] == 0).all() and (got["last_recv"] == host_upto[-1, recoded]).all()
+    for i, s in enumerate(recoded):
+        if s not in rejecting:
+            assert bytes(got["states"][i]) == bytes(ref["states"][i]) and (got["checksums"][:, i] == ref["checksums"][:, i]).all()
 
 
 def test_hosts_on_different_clocks_and_receives_queued_ahead(oracle):
